@@ -1,9 +1,11 @@
 #!/usr/bin/env python
 """Headline benchmark: training images/sec of the U-Net hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
         N>1 without a torchrun environment: bench.py re-launches itself as N ranks (one process per GPU, like the
         reference's Trainer(accelerator="ddp"), main.py:106-107) and FAILS if fewer than N GPUs / ranks come up.
+        A plain run sets up, warms up, times the K steps and prints the line; --dump-outputs writes what the last
+        timed step computed (dump_outputs); --full adds everything else below.
     python bench.py --phase encoder-forward --encoder resnest50 [--precision 16]
         north_star target figure: MFMA utilisation of the resnest50 encoder forward (model/unet.py:45-52).
 
@@ -11,7 +13,7 @@ N=1 workload = BASELINE.json configs[1]: --type pre --encoder resnet50 --loss_st
 fp32, synthetic tiles (seeded uniform-uint8 RGB normalised with ImageNet mean/std, rectangle masks), key-seeded
 random weights.  One step = forward + loss + backward (+ RCCL gradient all-reduce overlapped with backward when
 N>1) + fused AdamW step, everything through the HIP C ABI.  Weak scaling: per-GPU batch fixed.
-Rank 0 prints ONE JSON line (contract in the task statement) including
+Rank 0 prints ONE JSON line (contract in the task statement); with --full it also carries
   roofline:     dominant kernel's algorithmic conv FLOPs / its HIP-event time, against the fp32 MFMA peak
   cpu_baseline: the CPU oracle (PyTorch fp32 restatement of the reference path) timed on the host cores
                 (1 warm-up + median of 3 steps at the same shape),
@@ -403,6 +405,39 @@ def compact_line(out, detail_path=None):
     return c
 
 
+DUMP_SAMPLE = 1 << 20           # elements of the seeded samples of the parameter and gradient buffers
+DUMP_BUDGET = 15 << 20          # elements in all (60 MB in float32)
+
+
+def _seeded_sample(t, k):
+    """t flattened, or the same k elements of it (seeded, sorted indices) whenever t has more"""
+    flat = t.detach().reshape(-1)
+    if flat.numel() <= k:
+        return flat
+    idx = torch.randint(0, flat.numel(), (k,), generator=torch.Generator().manual_seed(0)).sort().values
+    return flat[idx.to(flat.device)]
+
+
+def dump_outputs(outdir, loss, pred, model, optim):
+    """--dump-outputs DIR: what the last timed step returned to its caller, as float32 DIR/<name>.npy -
+    loss; logits (and logits_aux<i> for the further deep-supervision outputs), whole or, above their share of the budget, a
+    seeded sample; params_sample / grads_sample: seeded samples of the updated flat parameters and of the step's gradients;
+    bn_running_stats: every BatchNorm running mean and variance after the step, in state_dict order"""
+    import numpy as np
+    preds = pred if isinstance(pred, (list, tuple)) else [pred]
+    stats = [b.detach().reshape(-1).float() for n, b in model.named_buffers()
+             if n.endswith("running_mean") or n.endswith("running_var")]
+    arrays = {"loss": loss.detach().reshape(1), "params_sample": _seeded_sample(optim.flat_p, DUMP_SAMPLE),
+              "grads_sample": _seeded_sample(optim.flat_g, DUMP_SAMPLE),
+              "bn_running_stats": _seeded_sample(torch.cat(stats), DUMP_SAMPLE) if stats else torch.zeros(0)}
+    share = (DUMP_BUDGET - 3 * DUMP_SAMPLE - 1) // len(preds)
+    for i, p in enumerate(preds):
+        arrays["logits" if i == 0 else "logits_aux%d" % i] = _seeded_sample(p, share)
+    os.makedirs(outdir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), t.float().cpu().numpy())
+
+
 def free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -787,7 +822,17 @@ def main():
     ap.add_argument("--share-gpu", action="store_true",
                     help="debug / test: all ranks share cuda:0 and gloo carries the device tensors (exercises the N>1 "
                          "code path on a 1-GPU box; the line is marked and is NOT a scaling measurement)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: roofline (HIP events around MFMA launches, also inside "
+                         "the timed steps), collectives probe, resnest50 encoder-forward probe, the other configurations' "
+                         "legs, split-form error check, CPU oracle baseline + first-step parity, detail file; the --no-* "
+                         "options switch parts of it off")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (see dump_outputs)")
     opt = ap.parse_args()
+    if not opt.full:
+        # a plain run: set up, warm up, time the steps, (dump), print the line
+        opt.no_prof = opt.no_cpu_baseline = opt.no_encoder_probe = opt.no_other_configs = opt.no_split_check = True
 
     if opt.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(opt.gpus)
@@ -926,8 +971,9 @@ def main():
         reducer = xdist.GradReducer(optim)
     for i in range(opt.warmup):
         l0 = run()
-        if i == 0 and graphed is None and world == 1:
+        if i == 0 and graphed is None and world == 1 and not opt.no_cpu_baseline:
             hip_first = grab_first(l0)
+    graph_pred = last.get("pred") if graphed is not None else None      # the captured output, rewritten by every replay
     last.clear()
 
     dom_kid = -1
@@ -956,10 +1002,12 @@ def main():
         barrier()
         dt = time.time() - t0
     xdist.check_peer_exchange()      # one-shot SyncBatchNorm exchange (XV2_SYNCBN=auto / oneshot): a timed-out exchange is an error
+    if opt.dump_outputs and rank == 0:
+        dump_outputs(opt.dump_outputs, loss, last.get("pred", graph_pred), model, optim)
     coll = None
-    if world > 1 and reducer.enabled and graphed is None:
+    if opt.full and world > 1 and reducer.enabled and graphed is None:
         coll = collectives_probe(optim, reducer, step, barrier, world, dt / opt.steps * 1e3)
-    if hip_first is None and world == 1 and graphed is None and opt.warmup == 0:
+    if hip_first is None and world == 1 and graphed is None and opt.warmup == 0 and not opt.no_cpu_baseline:
         sys.stderr.write("no warm-up step: the parity block needs the first step outside the timed region\n")
     rows, iso = [], []
     psteps = opt.steps
@@ -1152,7 +1200,8 @@ def main():
                     sys.stderr.write("PARITY GATE FAILED (%s): %s\n" % (leg["config"], json.dumps(leg["parity"])))
     for leg in out.get("other_configs", []) if rank == 0 else []:
         leg.pop("_first", None)
-    if rank == 0:
+    detail_path = None
+    if rank == 0 and opt.full:
         # the per-kernel tables, notes and prose go to a side file; the LAST stdout line is the compact record (< 6 KB)
         detail_path = os.environ.get("XV2_BENCH_DETAIL") or os.path.join(ROOT, "gpurun_out", "bench_detail.json")
         try:
@@ -1162,6 +1211,7 @@ def main():
         except OSError as e:
             sys.stderr.write("bench detail not written (%s)\n" % e)
             detail_path = None
+    if rank == 0:
         line = json.dumps(compact_line(out, detail_path), separators=(",", ":"))
         assert len(line) < COMPACT_LINE_MAX, len(line)
         sys.stdout.flush()

@@ -4,7 +4,7 @@
 A=$1; B=$2; shift 2
 for rep in 1 2; do
   for E in "$A" "$B"; do
-    env $E python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs --no-prof "$@" 2>/dev/null | python -c "
+    env $E python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs --no-prof "$@" 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 ef=d.get('encoder_forward') or []

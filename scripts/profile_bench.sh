@@ -8,7 +8,7 @@ OUT=$R/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/kt /tmp/pf /tmp/pw
-rocprofv3 --kernel-trace --stats -d /tmp/kt -o kt -- python $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-encoder-probe --no-split-check --no-other-configs "$@" > $OUT/bench_under_trace.json 2>/dev/null
+rocprofv3 --kernel-trace --stats -d /tmp/kt -o kt -- python $R/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-encoder-probe --no-split-check --no-other-configs "$@" > $OUT/bench_under_trace.json 2>/dev/null
 (cd $R && python scripts/rocpd_stats.py $(find /tmp/kt -name "*.db" | head -1) $OUT/kernel_stats.md > /dev/null)
 # the PMC passes (the headline configuration only; a pass that dies leaves the traffic file unwritten, nothing else)
 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d /tmp/pf -o pf -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-encoder-probe --no-prof --no-split-check --no-other-configs "$@" > /dev/null 2>&1 || echo "FETCH_SIZE pass failed"

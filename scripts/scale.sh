@@ -11,10 +11,10 @@ for N in 1 2 4 8; do
   [ "$N" -gt "$MAX" ] && break
   OUT=gpurun_out/scale_n${N}.json
   if [ "$N" = 1 ]; then
-    python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs --no-encoder-probe --no-split-check "$@" > $OUT 2> gpurun_out/scale_n${N}.err
+    python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs --no-encoder-probe --no-split-check "$@" > $OUT 2> ${OUT%.json}.err
   else
     python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $((29500 + N)) \
-      bench.py --gpus $N --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs --no-encoder-probe --no-split-check "$@" > $OUT 2> gpurun_out/scale_n${N}.err
+      bench.py --full --gpus $N --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs --no-encoder-probe --no-split-check "$@" > $OUT 2> ${OUT%.json}.err
   fi
   python - "$OUT" "$N" <<'PY'
 import json, sys

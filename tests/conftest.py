@@ -10,14 +10,6 @@ if os.path.dirname(os.path.abspath(__file__)) not in sys.path:
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 
-def _gpu_present():
-    try:
-        import torch
-        return torch.cuda.is_available()
-    except Exception:
-        return False
-
-
 def _cpu_threads(workers):
     """intra-op threads per test process.  The oracle passes of the parity tests are 64 x 64-tile networks: on the GPU
     box's 256 host threads torch's default (one OpenMP thread per core) spends its time in barriers - the round-2 suite
@@ -27,24 +19,21 @@ def _cpu_threads(workers):
 
 
 def _workers(config):
+    """xdist workers: none unless XV2_TEST_WORKERS asks for them (an explicit -n is left to xdist).  Every worker keeps
+    its own HIP context open for the whole run and a multi-rank test adds its rank processes on the same GPU; in one
+    process the suite holds the GPU in at most six processes at a time: the test process and at most 5 rank children
+    (tests/test_dist_gpu.py sizes its largest worlds to that)."""
     env = os.environ.get("XV2_TEST_WORKERS")
-    if env is not None:
-        return max(0, int(env))
-    if getattr(config.option, "numprocesses", None) is not None:      # -n given on the command line
+    if env is None or getattr(config.option, "numprocesses", None) is not None:
         return 0
-    expr = getattr(config.option, "markexpr", "") or ""
-    if "gpu" not in expr or "not gpu" in expr:
-        return 0
-    if (os.cpu_count() or 1) < 32 or not _gpu_present():
-        return 0
-    return 6
+    return max(0, int(env))
 
 
 @pytest.hookimpl(tryfirst=True)
 def pytest_cmdline_main(config):
-    """`pytest -m gpu` on the GPU box: spread the parity tests over 6 xdist workers (each with its own HIP context on
-    the one GPU and a bounded OpenMP team for its oracle passes).  xdist's own pytest_cmdline_main runs last and turns
-    numprocesses into worker specs.  XV2_TEST_WORKERS=0 keeps everything in one process."""
+    """`XV2_TEST_WORKERS=N pytest -m gpu`: spread the parity tests over N xdist workers (each with its own HIP context
+    on the one GPU and a bounded OpenMP team for its oracle passes).  xdist's own pytest_cmdline_main runs last and
+    turns numprocesses into worker specs.  Without the variable everything runs in one process."""
     if not config.pluginmanager.hasplugin("xdist") or os.environ.get("PYTEST_XDIST_WORKER"):
         return None
     n = _workers(config)

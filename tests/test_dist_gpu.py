@@ -196,10 +196,11 @@ def _spawn(target, world, args, timeout=900):
         assert p.exitcode == 0, "rank process exit code %s" % p.exitcode
 
 
-@pytest.mark.parametrize("world,total", [(4, 4), (8, 8)])
+@pytest.mark.parametrize("world,total", [(4, 4), (5, 5)])
 def test_many_ranks_with_syncbn_equal_one_process_with_the_global_batch(tmp_path, world, total):
-    """the same equivalence at world 4 and 8 (one image per rank): SyncBatchNorm statistics over the global batch, >= 8
-    gradient buckets, every rank ends with identical gradients and parameters"""
+    """the same equivalence at world 4 and 5 (one image per rank): SyncBatchNorm statistics over the global batch, >= 8
+    gradient buckets, every rank ends with identical gradients and parameters (world 5: the suite's bound of 5 rank
+    children per test, tests/conftest.py)"""
     _spawn(_two_rank_worker, world, (str(tmp_path), "resnet50", False, total))
     res = [torch.load(os.path.join(str(tmp_path), "rank%d.pt" % r), weights_only=False) for r in range(world)]
     _compare_with_global_batch(res, "resnet50", False, total)
@@ -340,7 +341,7 @@ def _peer_exchange_worker(rank, world, port, outdir):
         dist.destroy_process_group()
 
 
-@pytest.mark.parametrize("world", [2, 3, 4, 8])
+@pytest.mark.parametrize("world", [2, 3, 4, 5])
 def test_one_shot_peer_exchange_sums_in_rank_order_under_uneven_load(tmp_path, world):
     """include/xv2.h xv2_xchg_allreduce (the SyncBatchNorm statistics exchange without a collective call): `world`
     processes on cuda:0 map each other's exchange buffers over hipIpc; 300 exchanges of 1 .. 4096 doubles must equal the
@@ -451,16 +452,29 @@ def test_bench_two_ranks_sharing_the_gpu_run_the_whole_multi_rank_bench_path():
     """the N > 1 path of bench.py end to end on the 1-GPU box: self-launch through torch.distributed.run, rendezvous on
     127.0.0.1, SyncBatchNorm + bucketed gradient all-reduce in every step, barriers around the timed region, max over
     ranks, ONE line from rank 0 (gloo carries the device tensors: RCCL refuses two ranks on one device).  With RCCL the
-    same code runs at round end (`test_bench_self_launches_two_ranks_over_rccl`, needs 2 GPUs)"""
-    r, line = _run_bench("--gpus", "2", "--share-gpu", "--steps", "2", "--warmup", "1", "--size", "256", "--no-cpu-baseline")
+    same code runs at round end (`test_bench_self_launches_two_ranks_over_rccl`, needs 2 GPUs).  --full: also the
+    collectives probe and the HIP-event roofline of the multi-rank step"""
+    r, line = _run_bench("--full", "--gpus", "2", "--share-gpu", "--steps", "2", "--warmup", "1", "--size", "256",
+                         "--no-cpu-baseline")
     assert r.returncode == 0, (r.stderr[-2000:], r.stdout[-500:])
     assert sum(1 for ln in r.stdout.splitlines() if ln.startswith("{")) == 1
     assert line["n_gpus"] == 2 and line["n_ranks_seen"] == 2 and line["config"]["global_batch"] == 4
     assert line["value"] > 0 and line["scaling"] == "weak" and "SHARE" in line["config"]["parallelism"]
+    assert line["collectives"]["allreduce_bytes"] > 0 and line["collectives"]["buckets"] >= 1
+    assert line["roofline"] is not None and line["roofline"]["launches_timed"] > 0
+
+
+def test_plain_bench_run_with_two_ranks_sharing_the_gpu():
+    """the same multi-rank path as a plain run (no --full): the headline figure only, no collectives probe, no roofline"""
+    r, line = _run_bench("--gpus", "2", "--share-gpu", "--steps", "2", "--warmup", "1", "--size", "256")
+    assert r.returncode == 0, (r.stderr[-2000:], r.stdout[-500:])
+    assert sum(1 for ln in r.stdout.splitlines() if ln.startswith("{")) == 1
+    assert line["n_gpus"] == 2 and line["n_ranks_seen"] == 2 and line["config"]["global_batch"] == 4
+    assert line["value"] > 0 and "collectives" not in line and line["roofline"] is None
 
 
 def test_bench_line_carries_parity_roofline_and_encoder_probe_at_reduced_size(tmp_path):
-    """the default bench line at a reduced tile (256 x 256 so that the CPU oracle leg takes seconds): contract keys,
+    """the --full bench line at a reduced tile (256 x 256 so that the CPU oracle leg takes seconds): contract keys,
     the first-step parity block against the oracle and the resnest50 encoder-forward utilisation block; the line is the
     LAST stdout line and stays under 6 KB (the driver's parser lost the 25 KB line of round 5), the per-kernel tables
     and prose are in the detail file"""
@@ -468,7 +482,7 @@ def test_bench_line_carries_parity_roofline_and_encoder_probe_at_reduced_size(tm
     detail_path = str(tmp_path / "bench_detail.json")
     os.environ["XV2_BENCH_DETAIL"] = detail_path
     try:
-        r, line = _run_bench("--steps", "3", "--warmup", "2", "--size", "256", "--no-big-configs")
+        r, line = _run_bench("--full", "--steps", "3", "--warmup", "2", "--size", "256", "--no-big-configs")
     finally:
         os.environ.pop("XV2_BENCH_DETAIL", None)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -503,3 +517,38 @@ def test_bench_line_carries_parity_roofline_and_encoder_probe_at_reduced_size(tm
     detail = json.load(open(detail_path))
     assert detail["value"] == line["value"] and len(detail["roofline"]["per_kernel"]) >= 3
     assert "resnest50" in detail["other_configs"][0]["config"] and detail["other_configs"][0]["parity"]["pass"] is True
+
+
+def test_plain_bench_line_times_the_steps_and_dumps_the_last_step(tmp_path):
+    """a plain run (no --full): the contract keys and none of the --full blocks, no detail file; --dump-outputs writes the
+    last timed step's loss, logits, parameter and gradient samples and BatchNorm running statistics (float32, finite),
+    bit for bit the same in a second run with the same arguments"""
+    import numpy as np
+
+    import bench
+    from oracle import torch_ref
+    out = tmp_path / "dump"
+    r, line = _run_bench("--steps", "3", "--warmup", "1", "--size", "256", "--dump-outputs", str(out))
+    assert r.returncode == 0, r.stderr[-2000:]
+    r2, _ = _run_bench("--steps", "3", "--warmup", "1", "--size", "256", "--dump-outputs", str(tmp_path / "again"))
+    assert r2.returncode == 0, r2.stderr[-2000:]
+    assert sum(1 for ln in r.stdout.splitlines() if ln.startswith("{")) == 1
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup", "config"):
+        assert k in line, k
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["dtype"] == "f32" and line["higher_is_better"] is True
+    assert abs(line["value"] - 2 * 1e3 / line["ms_per_step"]) <= 1e-2 * line["value"]
+    for k in ("cpu_baseline", "parity", "encoder_forward", "other_configs", "split_form_error_vs_fp64", "collectives"):
+        assert k not in line, k
+    assert line["roofline"] is None and line["detail"] is None
+    arrays = {f.name: np.load(str(f)) for f in out.iterdir()}
+    assert set(arrays) == {"loss.npy", "logits.npy", "params_sample.npy", "grads_sample.npy", "bn_running_stats.npy"}
+    assert all(a.dtype == np.float32 and a.size > 0 and np.isfinite(a).all() for a in arrays.values())
+    assert arrays["logits.npy"].size == 2 * 2 * 256 * 256
+    assert abs(float(arrays["loss.npy"][0]) - line["loss"]) <= 1e-5 * abs(line["loss"])
+    again = {f.name: np.load(str(f)) for f in (tmp_path / "again").iterdir()}
+    assert set(again) == set(arrays) and all(np.array_equal(arrays[k], again[k]) for k in arrays)
+    # the logits are the LAST timed step's: the oracle's loss of them against the bench's masks is the line's loss
+    a = bench.make_args("resnet50", "pre", "dice")
+    _, mask = bench.synthetic_tiles(a, 2, 256, 1)
+    logits = torch.from_numpy(arrays["logits.npy"]).view(2, 2, 256, 256)
+    assert abs(float(torch_ref.Loss(a)(logits, mask)) - line["loss"]) <= 1e-4 * abs(line["loss"])
