@@ -511,6 +511,40 @@ int xv2_adamw_step_dev(float* param, const float* grad, float* exp_avg, float* e
                        const float* lr_dev, float beta1, float beta2, float eps, float weight_decay,
                        int* step_dev, float grad_scale, void* stream);
 
+/* The other --optimizer rules (model/plt.py:150-161) on the same flat buffers, graph-capturable like
+ * xv2_adamw_step_dev: lr and the step counter live in device memory, the call increments the counter.
+ * xv2_flat_step_dev: one elementwise launch (+ the counter increment); `rule`
+ *   0 sgd without momentum     model/plt.py:152  apex FusedSGD(lr, momentum=0)             (state0, state1 unused)
+ *   1 sgd with momentum        model/plt.py:152  apex FusedSGD(lr, momentum)                (state0 = momentum buffer)
+ *   2 radam                    model/plt.py:155  torch_optimizer RAdam(lr, weight_decay)    (state0/1 = exp_avg / exp_avg_sq)
+ *   3 adabelief                model/plt.py:156  torch_optimizer AdaBelief(lr, weight_decay) (state0/1 = exp_avg / exp_avg_var)
+ *   4 adabound                 model/plt.py:157  torch_optimizer AdaBound(lr, weight_decay) (state0/1 = exp_avg / exp_avg_sq;
+ *                                                base_lr = lr at construction, final_lr / gamma the package's)
+ * momentum is rule 1's, base_lr / final_lr / gamma rule 4's; the others ignore them.  The betas travel as double so
+ * that 1 - beta is formed before the rounding to fp32 (1 - 0.999f is 1.3e-5 away from 0.001). */
+int xv2_flat_step_dev(int rule, float* param, const float* grad, float* state0, float* state1, int64_t n,
+                      const float* lr_dev, int* step_dev, double beta1, double beta2, float eps, float weight_decay,
+                      float momentum, float base_lr, float final_lr, float gamma, float grad_scale, void* stream);
+
+/* Segmented rules: rows = int64 [rows_total][3] {first element, length, tensor} (one row per dim-0 slice of a tensor
+ * with >= 2 dims, one row per other tensor), tensors = int64 [ntensors][4] {first row, rows, numel, dims >= 2},
+ * partials = float [rows_total][4] scratch.  Three launches (row sums, per-tensor fold, apply) + the counter increment;
+ * fixed reduction order, no atomics.
+ * xv2_adamp_step_dev replaces model/plt.py:158 torch_optimizer AdamP(lr, weight_decay) (delta, wd_ratio the
+ * package's defaults); decision = int [ntensors] (0 no projection, 1 channel view, 2 layer view of the step),
+ * aux = float [ntensors][2] scratch. */
+int xv2_adamp_step_dev(const int64_t* rows, int64_t rows_total, const int64_t* tensors, int ntensors,
+                       float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* partials,
+                       int* decision, float* aux, const float* lr_dev, int* step_dev, double beta1, double beta2,
+                       float eps, float weight_decay, float delta, float wd_ratio, float grad_scale, void* stream);
+
+/* replaces model/plt.py:159 apex FusedNovoGrad(lr, weight_decay): norm_avg = float [ntensors], the blended per-tensor
+ * gradient norm (the step-1 launch sets it to the first norm) */
+int xv2_novograd_step_dev(const int64_t* rows, int64_t rows_total, const int64_t* tensors, int ntensors,
+                          float* param, const float* grad, float* exp_avg, float* norm_avg, float* partials,
+                          const float* lr_dev, int* step_dev, double beta1, double beta2, float eps,
+                          float weight_decay, float grad_scale, void* stream);
+
 /* ---- in-library kernel timing (bench.py roofline leg) --------------------------------------
  * When enabled, every launch of an MFMA kernel (implicit-GEMM conv / weight-gradient) is bracketed
  * by hipEvents on its own stream and tagged with its algorithmic FLOP count (2*M*N*K of the

@@ -1,0 +1,425 @@
+// The --optimizer choices other than AdamW (model/plt.py:150-161) on the flat fp32 parameter / gradient buffers of
+// xview2_amd.optim.  Every entry point reads the learning rate and the step counter from device memory and increments
+// the counter in its last launch, so a captured training step stays valid while the schedule advances.
+//
+// Elementwise rules (sgd, radam, adabelief, adabound): one grid-stride launch, the per-step scalars (bias corrections,
+// RAdam's rho_t and its branch, AdaBound's bounds) computed per thread in double from the step counter.
+//
+// Rules with per-tensor / per-output-channel reductions (adamp, novograd): a segment table built once per optimizer cuts
+// the buffer into rows (dim 0 of a tensor with >= 2 dims, else the whole tensor).  One wave per row sums a row's
+// products into `partials` (a fixed lane-strided order and a fixed butterfly: no atomics, bitwise-reproducible steps),
+// one wave per tensor folds its rows in a fixed order, one wave per row applies the update.
+#include "xv2_common.h"
+#include <algorithm>
+
+namespace xv2 {
+
+enum FlatRule { RULE_SGD = 0, RULE_SGD_MOMENTUM = 1, RULE_RADAM = 2, RULE_ADABELIEF = 3, RULE_ADABOUND = 4 };
+
+// the per-step scalars of one rule, computed in double from lr and the 1-based step, handed to the element loop as float
+struct StepScalars {
+    float a, b, c, d;
+};
+
+template <int R>
+__device__ __forceinline__ StepScalars step_scalars(double lr, double t, double b1, double b2, double wd, double mu,
+                                                    double base_lr, double final_lr, double gamma) {
+    StepScalars s{};
+    if (R == RULE_SGD) {
+        s.a = (float)lr;
+    } else if (R == RULE_SGD_MOMENTUM) {
+        s.a = (float)lr;
+        s.b = (float)mu;
+        s.c = t == 1.0 ? 0.f : 1.f;                 // the buffer starts as a copy of the first gradient
+    } else {
+        const double bc1 = 1.0 - pow(b1, t), bc2 = 1.0 - pow(b2, t);
+        if (R == RULE_RADAM) {
+            const double rho_inf = 2.0 / (1.0 - b2) - 1.0;
+            const double rho_t = rho_inf - 2.0 * t * pow(b2, t) / bc2;
+            s.a = (float)(1.0 - lr * wd);
+            if (rho_t >= 5.0) {
+                const double rt = sqrt(bc2 * (rho_t - 4.0) * (rho_t - 2.0) * rho_inf /
+                                       ((rho_inf - 4.0) * (rho_inf - 2.0) * rho_t));
+                s.b = (float)(lr * rt / bc1);
+                s.c = 1.f;                          // adaptive branch
+            } else {
+                s.b = (float)(lr / bc1);
+                s.c = 0.f;                          // un-rectified (momentum only) branch
+            }
+        } else if (R == RULE_ADABELIEF) {
+            s.a = (float)(lr / bc1);
+            s.b = (float)sqrt(bc2);
+        } else {                                    // RULE_ADABOUND
+            const double f = final_lr * lr / base_lr;
+            s.a = (float)(lr * sqrt(bc2) / bc1);
+            s.b = (float)(f * (1.0 - 1.0 / (gamma * t + 1.0)));
+            s.c = (float)(f * (1.0 + 1.0 / (gamma * t)));
+        }
+    }
+    return s;
+}
+
+// one element's update (shared by the 16-byte and the scalar loops: the same operations in the same order)
+template <int R>
+__device__ __forceinline__ void rule_one(float& p, float g, float& s0, float& s1, const StepScalars& k, float b1, float b2,
+                                         float c1, float c2, float eps, float wd, float gscale) {
+    float gi = g * gscale;
+    if (R == RULE_SGD) {
+        p -= k.a * gi;
+    } else if (R == RULE_SGD_MOMENTUM) {
+        const float buf = k.c != 0.f ? k.b * s0 + gi : gi;
+        s0 = buf;
+        p -= k.a * buf;
+    } else if (R == RULE_RADAM) {
+        const float pi = p * k.a;
+        const float mi = b1 * s0 + c1 * gi;
+        const float vi = b2 * s1 + c2 * gi * gi;
+        s0 = mi;
+        s1 = vi;
+        p = k.c != 0.f ? pi - k.b * (mi / (sqrtf(vi) + eps)) : pi - k.b * mi;
+    } else if (R == RULE_ADABELIEF) {
+        gi += wd * p;
+        const float mi = b1 * s0 + c1 * gi;
+        const float d = gi - mi;
+        const float si = (b2 * s1 + c2 * d * d) + eps;
+        s0 = mi;
+        s1 = si;
+        p -= k.a * (mi / (sqrtf(si) / k.b + eps));
+    } else {                                        // RULE_ADABOUND
+        gi += wd * p;
+        const float mi = b1 * s0 + c1 * gi;
+        const float vi = b2 * s1 + c2 * gi * gi;
+        s0 = mi;
+        s1 = vi;
+        const float step = fminf(fmaxf(k.a / (sqrtf(vi) + eps), k.b), k.c);
+        p -= step * mi;
+    }
+}
+
+template <int R>
+__global__ void __launch_bounds__(256) flat_rule_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                         float* __restrict__ s0, float* __restrict__ s1, int64_t n,
+                                                         const float* __restrict__ lr_dev, const int* __restrict__ step_dev,
+                                                         double b1d, double b2d, float eps, float wd, float mu,
+                                                         float base_lr, float final_lr, float gamma, float gscale) {
+    const double t = (double)(step_dev[0] + 1);
+    const StepScalars k = step_scalars<R>((double)lr_dev[0], t, b1d, b2d, wd, mu, base_lr, final_lr, gamma);
+    // the betas and their complements rounded once from double (1 - 0.999f would be 1.3e-5 off 0.001)
+    const float b1 = (float)b1d, b2 = (float)b2d, c1 = (float)(1.0 - b1d), c2 = (float)(1.0 - b2d);
+    constexpr bool has0 = R != RULE_SGD, has1 = R != RULE_SGD && R != RULE_SGD_MOMENTUM;
+    float z0 = 0.f, z1 = 0.f;                        // stand-ins for the state a rule does not keep
+    const int64_t n4 = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(s0) |
+                         reinterpret_cast<uintptr_t>(s1)) & 15) ? 0 : n >> 2;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+        float4 pp = reinterpret_cast<float4*>(p)[i];
+        const float4 gg = reinterpret_cast<const float4*>(g)[i];
+        float4 a = has0 ? reinterpret_cast<float4*>(s0)[i] : float4{0.f, 0.f, 0.f, 0.f};
+        float4 b = has1 ? reinterpret_cast<float4*>(s1)[i] : float4{0.f, 0.f, 0.f, 0.f};
+        rule_one<R>(pp.x, gg.x, a.x, b.x, k, b1, b2, c1, c2, eps, wd, gscale);
+        rule_one<R>(pp.y, gg.y, a.y, b.y, k, b1, b2, c1, c2, eps, wd, gscale);
+        rule_one<R>(pp.z, gg.z, a.z, b.z, k, b1, b2, c1, c2, eps, wd, gscale);
+        rule_one<R>(pp.w, gg.w, a.w, b.w, k, b1, b2, c1, c2, eps, wd, gscale);
+        if (has0) reinterpret_cast<float4*>(s0)[i] = a;
+        if (has1) reinterpret_cast<float4*>(s1)[i] = b;
+        reinterpret_cast<float4*>(p)[i] = pp;
+    }
+    for (int64_t i = n4 * 4 + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        rule_one<R>(p[i], g[i], has0 ? s0[i] : z0, has1 ? s1[i] : z1, k, b1, b2, c1, c2, eps, wd, gscale);
+}
+
+__global__ void inc_step_kernel(int* p) { p[0] += 1; }
+
+// ---- segmented rules --------------------------------------------------------------------------------------------
+// rows  [rows_total][3] int64: {first element, length, tensor}
+// tens  [ntensors][4]   int64: {first row, rows, numel, dims >= 2}
+// partials [rows_total][SEG_K] float
+constexpr int SEG_K = 4;
+constexpr int SEG_WAVES = 4;                         // waves (rows or tensors) per 256-thread block
+enum SegRule { SEG_ADAMP = 0, SEG_NOVOGRAD = 1 };
+
+__device__ __forceinline__ double wave_max(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+    return v;
+}
+
+struct AdamPScalars {
+    float b1, b2, c1, c2, eps, bc2s, gscale;
+};
+
+// AdamP's row pass for one element: moments updated, then sum p*g, g*g, p*p, p*u (u the Adam direction)
+__device__ __forceinline__ void adamp_row_one(float p, float g, float& m, float& v, const AdamPScalars& c, double (&acc)[SEG_K]) {
+    const float gi = g * c.gscale;
+    const float mi = c.b1 * m + c.c1 * gi;
+    const float vi = c.b2 * v + c.c2 * gi * gi;
+    m = mi;
+    v = vi;
+    const float u = mi / (sqrtf(vi) / c.bc2s + c.eps);
+    acc[0] += (double)p * gi;
+    acc[1] += (double)gi * gi;
+    acc[2] += (double)p * p;
+    acc[3] += (double)p * u;
+}
+
+template <int S>
+__global__ void __launch_bounds__(256) seg_row_kernel(const int64_t* __restrict__ rows, int64_t rows_total,
+                                                       const float* __restrict__ p, const float* __restrict__ g,
+                                                       float* __restrict__ m, float* __restrict__ v,
+                                                       float* __restrict__ partials, const int* __restrict__ step_dev,
+                                                       double b1, double b2, float eps, float gscale) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * SEG_WAVES + (threadIdx.x >> 6);
+    if (row >= rows_total) return;
+    const int64_t start = rows[row * 3], len = rows[row * 3 + 1];
+    double acc[SEG_K] = {0.0, 0.0, 0.0, 0.0};
+    const bool vec = (len & 3) == 0 && (start & 3) == 0;
+    if (S == SEG_ADAMP) {
+        const double t = (double)(step_dev[0] + 1);
+        const AdamPScalars c{(float)b1, (float)b2, (float)(1.0 - b1), (float)(1.0 - b2), eps, (float)sqrt(1.0 - pow(b2, t)), gscale};
+        if (vec) {
+            const int64_t l4 = len >> 2, s4 = start >> 2;
+            for (int64_t i = lane; i < l4; i += 64) {
+                const float4 pp = reinterpret_cast<const float4*>(p)[s4 + i];
+                const float4 gg = reinterpret_cast<const float4*>(g)[s4 + i];
+                float4 mm = reinterpret_cast<float4*>(m)[s4 + i], vv = reinterpret_cast<float4*>(v)[s4 + i];
+                adamp_row_one(pp.x, gg.x, mm.x, vv.x, c, acc);
+                adamp_row_one(pp.y, gg.y, mm.y, vv.y, c, acc);
+                adamp_row_one(pp.z, gg.z, mm.z, vv.z, c, acc);
+                adamp_row_one(pp.w, gg.w, mm.w, vv.w, c, acc);
+                reinterpret_cast<float4*>(m)[s4 + i] = mm;
+                reinterpret_cast<float4*>(v)[s4 + i] = vv;
+            }
+        } else {
+            for (int64_t i = lane; i < len; i += 64) adamp_row_one(p[start + i], g[start + i], m[start + i], v[start + i], c, acc);
+        }
+    } else {                                         // SEG_NOVOGRAD: the squared norm of the scaled gradient
+        if (vec) {
+            const int64_t l4 = len >> 2, s4 = start >> 2;
+            for (int64_t i = lane; i < l4; i += 64) {
+                const float4 gg = reinterpret_cast<const float4*>(g)[s4 + i];
+                const float x = gg.x * gscale, y = gg.y * gscale, z = gg.z * gscale, w = gg.w * gscale;
+                acc[1] += (double)x * x + (double)y * y + (double)z * z + (double)w * w;
+            }
+        } else {
+            for (int64_t i = lane; i < len; i += 64) {
+                const float x = g[start + i] * gscale;
+                acc[1] += (double)x * x;
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < SEG_K; ++k) acc[k] = wave_sum(acc[k]);
+    if (lane < SEG_K) partials[row * SEG_K + lane] = (float)acc[lane];
+}
+
+// |cos| as F.cosine_similarity(g, p, eps) computes it: each norm clamped below at eps
+__device__ __forceinline__ double abs_cos(double pg, double gg, double pp, double eps) {
+    return fabs(pg) / (fmax(sqrt(gg), eps) * fmax(sqrt(pp), eps));
+}
+
+// one wave per tensor.  AdamP: decision[t] (0 no projection, 1 channel view, 2 layer view) and aux[t] = {layer-view
+// coefficient sum(p*u) / (|p| + eps)^2, weight-decay ratio}.  NovoGrad: the blended gradient norm norm_avg[t].
+template <int S>
+__global__ void __launch_bounds__(256) seg_fold_kernel(const int64_t* __restrict__ tens, int ntensors,
+                                                        const float* __restrict__ partials, int* __restrict__ decision,
+                                                        float* __restrict__ aux, float* __restrict__ norm_avg,
+                                                        const int* __restrict__ step_dev, double b2, float eps, float delta,
+                                                        float wd_ratio) {
+    const int lane = threadIdx.x & 63;
+    const int tsr = blockIdx.x * SEG_WAVES + (threadIdx.x >> 6);
+    if (tsr >= ntensors) return;                     // (wave-uniform: a wave owns one tensor)
+    const int64_t r0 = tens[tsr * 4], nr = tens[tsr * 4 + 1], numel = tens[tsr * 4 + 2];
+    const bool multi_dim = tens[tsr * 4 + 3] != 0;
+    double acc[SEG_K] = {0.0, 0.0, 0.0, 0.0};
+    double mx = 0.0;
+    for (int64_t r = lane; r < nr; r += 64) {
+        const float* q = partials + (r0 + r) * SEG_K;
+#pragma unroll
+        for (int k = 0; k < SEG_K; ++k) acc[k] += (double)q[k];
+        if (S == SEG_ADAMP) mx = fmax(mx, abs_cos(q[0], q[1], q[2], eps));
+    }
+#pragma unroll
+    for (int k = 0; k < SEG_K; ++k) acc[k] = wave_sum(acc[k]);
+    if (S == SEG_ADAMP) mx = wave_max(mx);
+    if (lane != 0) return;
+    if (S == SEG_ADAMP) {
+        const int64_t rowlen = numel / nr;
+        int dec = 0;
+        double coef = 0.0;
+        if (multi_dim) {
+            if (mx < (double)delta / sqrt((double)rowlen)) {
+                dec = 1;                             // channel view: the apply pass takes each row's own coefficient
+            } else if (abs_cos(acc[0], acc[1], acc[2], eps) < (double)delta / sqrt((double)numel)) {
+                dec = 2;
+                const double pn = sqrt(acc[2]) + eps;
+                coef = acc[3] / (pn * pn);
+            }
+        }
+        decision[tsr] = dec;
+        aux[tsr * 2] = (float)coef;
+        aux[tsr * 2 + 1] = dec ? wd_ratio : 1.f;
+    } else {
+        const double n = sqrt(acc[1]);
+        const double prev = norm_avg[tsr];
+        norm_avg[tsr] = step_dev[0] == 0 ? (float)n : (float)sqrt(b2 * prev * prev + (1.0 - b2) * n * n);
+    }
+}
+
+struct ApplyScalars {
+    float lr, step_size, bc2s, b1, c1, eps, wd, gscale;
+};
+
+// AdamP: u from the moments the row pass stored, projected by `coef`, decoupled decay scaled by the tensor's ratio
+__device__ __forceinline__ void adamp_apply_one(float& p, float m, float v, float coef, float decay, const ApplyScalars& c) {
+    const float u = m / (sqrtf(v) / c.bc2s + c.eps) - coef * p;
+    p = p * decay - c.step_size * u;
+}
+// NovoGrad (grad averaging, decay outside the moment): `den` = norm_avg / sqrt(1 - b2^t) + eps of the tensor
+__device__ __forceinline__ void novograd_apply_one(float& p, float g, float& m, float den, const ApplyScalars& c) {
+    const float gi = g * c.gscale;
+    const float mi = c.b1 * m + c.c1 * gi;
+    m = mi;
+    p = p - c.lr * ((mi * c.step_size) / den + c.wd * p);
+}
+
+template <int S>
+__global__ void __launch_bounds__(256) seg_apply_kernel(const int64_t* __restrict__ rows, int64_t rows_total,
+                                                         float* __restrict__ p, const float* __restrict__ g,
+                                                         float* __restrict__ m, const float* __restrict__ v,
+                                                         const float* __restrict__ partials,
+                                                         const int* __restrict__ decision, const float* __restrict__ aux,
+                                                         const float* __restrict__ norm_avg,
+                                                         const float* __restrict__ lr_dev, const int* __restrict__ step_dev,
+                                                         double b1, double b2, float eps, float wd, float gscale) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * SEG_WAVES + (threadIdx.x >> 6);
+    if (row >= rows_total) return;
+    const int64_t start = rows[row * 3], len = rows[row * 3 + 1], tsr = rows[row * 3 + 2];
+    const double lr = lr_dev[0], t = (double)(step_dev[0] + 1);
+    const double bc1 = 1.0 - pow(b1, t), bc2s = sqrt(1.0 - pow(b2, t));
+    ApplyScalars c{(float)lr, 0.f, (float)bc2s, (float)b1, (float)(1.0 - b1), eps, wd, gscale};
+    const bool vec = (len & 3) == 0 && (start & 3) == 0;
+    const int64_t l4 = len >> 2, s4 = start >> 2;
+    if (S == SEG_ADAMP) {
+        c.step_size = (float)(lr / bc1);
+        const int dec = decision[tsr];
+        float coef = 0.f;
+        if (dec == 1) {
+            const float* q = partials + row * SEG_K;
+            const double pn = sqrt((double)q[2]) + eps;
+            coef = (float)((double)q[3] / (pn * pn));
+        } else if (dec == 2) {
+            coef = aux[tsr * 2];
+        }
+        const float decay = (float)(1.0 - lr * wd * (double)aux[tsr * 2 + 1]);
+        if (vec) {
+            for (int64_t i = lane; i < l4; i += 64) {
+                float4 pp = reinterpret_cast<float4*>(p)[s4 + i];
+                const float4 mm = reinterpret_cast<const float4*>(m)[s4 + i], vv = reinterpret_cast<const float4*>(v)[s4 + i];
+                adamp_apply_one(pp.x, mm.x, vv.x, coef, decay, c);
+                adamp_apply_one(pp.y, mm.y, vv.y, coef, decay, c);
+                adamp_apply_one(pp.z, mm.z, vv.z, coef, decay, c);
+                adamp_apply_one(pp.w, mm.w, vv.w, coef, decay, c);
+                reinterpret_cast<float4*>(p)[s4 + i] = pp;
+            }
+        } else {
+            for (int64_t i = lane; i < len; i += 64) adamp_apply_one(p[start + i], m[start + i], v[start + i], coef, decay, c);
+        }
+    } else {
+        c.step_size = (float)(1.0 / bc1);
+        const float den = (float)((double)norm_avg[tsr] / bc2s + eps);
+        if (vec) {
+            for (int64_t i = lane; i < l4; i += 64) {
+                float4 pp = reinterpret_cast<float4*>(p)[s4 + i], mm = reinterpret_cast<float4*>(m)[s4 + i];
+                const float4 gg = reinterpret_cast<const float4*>(g)[s4 + i];
+                novograd_apply_one(pp.x, gg.x, mm.x, den, c);
+                novograd_apply_one(pp.y, gg.y, mm.y, den, c);
+                novograd_apply_one(pp.z, gg.z, mm.z, den, c);
+                novograd_apply_one(pp.w, gg.w, mm.w, den, c);
+                reinterpret_cast<float4*>(m)[s4 + i] = mm;
+                reinterpret_cast<float4*>(p)[s4 + i] = pp;
+            }
+        } else {
+            for (int64_t i = lane; i < len; i += 64) novograd_apply_one(p[start + i], g[start + i], m[start + i], den, c);
+        }
+    }
+}
+
+}  // namespace xv2
+
+using namespace xv2;
+
+extern "C" int xv2_flat_step_dev(int rule, float* param, const float* grad, float* state0, float* state1, int64_t n,
+                                 const float* lr_dev, int* step_dev, double beta1, double beta2, float eps,
+                                 float weight_decay, float momentum, float base_lr, float final_lr, float gamma,
+                                 float grad_scale, void* stream) {
+    XV2_CHECK_ARG(param && grad && lr_dev && step_dev && n > 0, "flat_step_dev: null buffer or empty");
+    XV2_CHECK_ARG(rule >= RULE_SGD && rule <= RULE_ADABOUND, "flat_step_dev: unknown rule %d", rule);
+    XV2_CHECK_ARG(rule == RULE_SGD || state0, "flat_step_dev: rule %d keeps a first state buffer", rule);
+    XV2_CHECK_ARG(rule == RULE_SGD || rule == RULE_SGD_MOMENTUM || state1, "flat_step_dev: rule %d keeps two state buffers", rule);
+    XV2_CHECK_ARG(rule != RULE_ADABOUND || base_lr > 0.f, "flat_step_dev: adabound needs base_lr > 0");
+    const int grid = (int)std::min<int64_t>(cdiv(cdiv(n, 4), 256), 4096);
+    hipStream_t s = (hipStream_t)stream;
+#define XV2_RULE_LAUNCH(R)                                                                                             \
+    hipLaunchKernelGGL(flat_rule_kernel<R>, dim3(grid), dim3(256), 0, s, param, grad, state0, state1, n, lr_dev,     \
+                       step_dev, beta1, beta2, eps, weight_decay, momentum, base_lr, final_lr, gamma, grad_scale)
+    switch (rule) {
+        case RULE_SGD: XV2_RULE_LAUNCH(RULE_SGD); break;
+        case RULE_SGD_MOMENTUM: XV2_RULE_LAUNCH(RULE_SGD_MOMENTUM); break;
+        case RULE_RADAM: XV2_RULE_LAUNCH(RULE_RADAM); break;
+        case RULE_ADABELIEF: XV2_RULE_LAUNCH(RULE_ADABELIEF); break;
+        default: XV2_RULE_LAUNCH(RULE_ADABOUND);
+    }
+#undef XV2_RULE_LAUNCH
+    XV2_CHECK_LAUNCH();
+    hipLaunchKernelGGL(inc_step_kernel, dim3(1), dim3(1), 0, s, step_dev);
+    XV2_CHECK_LAUNCH();
+    return XV2_OK;
+}
+
+extern "C" int xv2_adamp_step_dev(const int64_t* rows, int64_t rows_total, const int64_t* tensors, int ntensors,
+                                  float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* partials,
+                                  int* decision, float* aux, const float* lr_dev, int* step_dev, double beta1, double beta2,
+                                  float eps, float weight_decay, float delta, float wd_ratio, float grad_scale,
+                                  void* stream) {
+    XV2_CHECK_ARG(rows && tensors && param && grad && exp_avg && exp_avg_sq && partials && decision && aux && lr_dev &&
+                  step_dev && rows_total > 0 && ntensors > 0, "adamp_step_dev: null buffer or empty table");
+    hipStream_t s = (hipStream_t)stream;
+    const unsigned rgrid = (unsigned)cdiv(rows_total, SEG_WAVES), tgrid = (unsigned)cdiv(ntensors, SEG_WAVES);
+    hipLaunchKernelGGL(seg_row_kernel<SEG_ADAMP>, dim3(rgrid), dim3(256), 0, s, rows, rows_total, param, grad, exp_avg,
+                       exp_avg_sq, partials, step_dev, beta1, beta2, eps, grad_scale);
+    XV2_CHECK_LAUNCH();
+    hipLaunchKernelGGL(seg_fold_kernel<SEG_ADAMP>, dim3(tgrid), dim3(256), 0, s, tensors, ntensors, partials, decision, aux,
+                       (float*)nullptr, step_dev, beta2, eps, delta, wd_ratio);
+    XV2_CHECK_LAUNCH();
+    hipLaunchKernelGGL(seg_apply_kernel<SEG_ADAMP>, dim3(rgrid), dim3(256), 0, s, rows, rows_total, param, grad, exp_avg,
+                       exp_avg_sq, partials, decision, aux, (const float*)nullptr, lr_dev, step_dev, beta1, beta2, eps,
+                       weight_decay, grad_scale);
+    XV2_CHECK_LAUNCH();
+    hipLaunchKernelGGL(inc_step_kernel, dim3(1), dim3(1), 0, s, step_dev);
+    XV2_CHECK_LAUNCH();
+    return XV2_OK;
+}
+
+extern "C" int xv2_novograd_step_dev(const int64_t* rows, int64_t rows_total, const int64_t* tensors, int ntensors,
+                                     float* param, const float* grad, float* exp_avg, float* norm_avg, float* partials,
+                                     const float* lr_dev, int* step_dev, double beta1, double beta2, float eps,
+                                     float weight_decay, float grad_scale, void* stream) {
+    XV2_CHECK_ARG(rows && tensors && param && grad && exp_avg && norm_avg && partials && lr_dev && step_dev &&
+                  rows_total > 0 && ntensors > 0, "novograd_step_dev: null buffer or empty table");
+    hipStream_t s = (hipStream_t)stream;
+    const unsigned rgrid = (unsigned)cdiv(rows_total, SEG_WAVES), tgrid = (unsigned)cdiv(ntensors, SEG_WAVES);
+    hipLaunchKernelGGL(seg_row_kernel<SEG_NOVOGRAD>, dim3(rgrid), dim3(256), 0, s, rows, rows_total, param, grad,
+                       (float*)nullptr, (float*)nullptr, partials, step_dev, beta1, beta2, eps, grad_scale);
+    XV2_CHECK_LAUNCH();
+    hipLaunchKernelGGL(seg_fold_kernel<SEG_NOVOGRAD>, dim3(tgrid), dim3(256), 0, s, tensors, ntensors, partials,
+                       (int*)nullptr, (float*)nullptr, norm_avg, step_dev, beta2, eps, 0.f, 1.f);
+    XV2_CHECK_LAUNCH();
+    hipLaunchKernelGGL(seg_apply_kernel<SEG_NOVOGRAD>, dim3(rgrid), dim3(256), 0, s, rows, rows_total, param, grad,
+                       exp_avg, (const float*)nullptr, partials, (const int*)nullptr, (const float*)nullptr, norm_avg,
+                       lr_dev, step_dev, beta1, beta2, eps, weight_decay, grad_scale);
+    XV2_CHECK_LAUNCH();
+    hipLaunchKernelGGL(inc_step_kernel, dim3(1), dim3(1), 0, s, step_dev);
+    XV2_CHECK_LAUNCH();
+    return XV2_OK;
+}

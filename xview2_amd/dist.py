@@ -1,7 +1,7 @@
 """Data-parallel training over RCCL/xGMI: one process per GPU (reference: Trainer(accelerator="ddp",
 sync_batchnorm=gpus > 1), main.py:106-107).
 
-* Gradients live in the flat buffer of ``FlatAdamW``; it is cut into buckets in REVERSE parameter order (the
+* Gradients live in the flat buffer of a ``FlatOptimizer``; it is cut into buckets in REVERSE parameter order (the
   order backward produces them).  A per-parameter post-accumulate hook counts a bucket down; when its last
   gradient has been written, the bucket slice is all-reduced (SUM) on a side HIP stream, fenced by events, so
   the collective overlaps with the rest of backward.  The 1/world averaging is folded into the optimizer

@@ -1,9 +1,9 @@
-"""Whole-step hipGraph capture: forward + loss + backward (+ RCCL all-reduce) + AdamW as ONE graph launch.
+"""Whole-step hipGraph capture: forward + loss + backward (+ RCCL all-reduce) + optimizer step as ONE graph launch.
 
 A training step of the U-Net issues ~1500 small-to-medium kernels; replaying them from a captured hipGraph removes
 the per-launch host cost and the inter-kernel gaps.  Requirements met by the HIP path: no allocation or
 synchronisation inside the C ABI, the optimizer's learning rate / step counter live in device memory
-(``FlatAdamW.capturable``), inputs are copied into static buffers before each replay.
+(``FlatOptimizer.capturable``), inputs are copied into static buffers before each replay.
 """
 import torch
 

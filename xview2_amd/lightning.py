@@ -4,7 +4,7 @@ What is kept is the SURFACE a user of the reference touches - ``Model(args)``, t
 Lightning-style trainer calls, ``configure_optimizers``, ``add_model_specific_args`` (every flag, choice and default of
 model/plt.py:181-234) and the artefacts written during evaluation (dllogger-style JSON lines, ``.npy`` probabilities
 with ``_target.png`` label maps, model/plt.py:105-144).  The implementation underneath is this package's: the
-networks and the loss run through the HIP C ABI, AdamW is the flat fused optimizer, F1 bookkeeping is one counting
+networks and the loss run through the HIP C ABI, every optimizer is a flat fused one, F1 bookkeeping is one counting
 launch per batch.  pytorch_lightning is not installed in this image; when it is importable ``Model`` derives from
 ``pl.LightningModule``, otherwise from a small stand-in driven by xview2_amd.trainer.
 """
@@ -17,7 +17,7 @@ import torch
 from torch import nn
 
 from . import criterion, networks, ops
-from .optim import FlatAdamW
+from .optim import make_flat_optimizer
 from .utils.f1 import F1
 from .utils.scheduler import NoamLR
 
@@ -228,19 +228,9 @@ class Model(_Base):
 
     # ---- optimizer / schedule -----------------------------------------------------------------------------------
     def configure_optimizers(self):
-        """model/plt.py:150-179.  AdamW (the default) is the flat fused HIP optimizer; sgd / adam / radam map to
-        torch.optim; the apex / torch_optimizer-only choices are rejected with a clear message."""
-        name, wd = self.args.optimizer.lower(), self.args.weight_decay
-        if name == "adamw":
-            optimizer = FlatAdamW(self.parameters(), lr=self.lr, weight_decay=wd)
-        else:
-            builders = {"sgd": lambda p: torch.optim.SGD(p, lr=self.lr, momentum=self.args.momentum),
-                        "adam": lambda p: torch.optim.Adam(p, lr=self.lr, weight_decay=wd),
-                        "radam": lambda p: torch.optim.RAdam(p, lr=self.lr, weight_decay=wd)}
-            if name not in builders:
-                raise NotImplementedError("--optimizer %s needs apex/torch_optimizer, which are CUDA-only / absent; "
-                                          "use adamw (default), adam, sgd or radam" % name)
-            optimizer = builders[name](self.parameters())
+        """model/plt.py:150-179.  Every --optimizer choice is a flat fused HIP optimizer (xview2_amd.optim)."""
+        optimizer = make_flat_optimizer(self.args.optimizer, self.parameters(), lr=self.lr,
+                                        weight_decay=self.args.weight_decay, momentum=self.args.momentum)
         if not self.args.use_scheduler:
             return optimizer
         # model/plt.py:170 uses len(self.train_dataloader()) // gpus on the UNSHARDED loader; here the trainer hands

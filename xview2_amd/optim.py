@@ -1,17 +1,23 @@
-"""AdamW on one flat parameter/gradient buffer: one HIP launch per step (model/plt.py:154 uses
-torch.optim.AdamW as the default --optimizer; same update rule, decoupled weight decay).
+"""The --optimizer choices (model/plt.py:150-161) on one flat parameter/gradient buffer: each rule is one HIP launch per
+step (AdamW, the default, and sgd / radam / adabelief / adabound) or three (adamp, novograd: per-tensor reductions), plus
+the device step-counter increment.
 
 All parameters are re-pointed at views of a single fp32 buffer and their ``.grad`` at views of a second one,
-so (a) the optimizer step is a single streaming kernel over 4 arrays, (b) the data-parallel reducer
-(xview2_amd.dist) all-reduces contiguous slices without packing copies.
+so (a) the optimizer step is a single streaming kernel over the parameter, gradient and state arrays, (b) the
+data-parallel reducer (xview2_amd.dist) all-reduces contiguous slices without packing copies.
 """
 import torch
 
 from . import ops
 
 
-class FlatAdamW:
-    def __init__(self, params, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+class FlatOptimizer:
+    """The flat buffers, the gradient slots the HIP backward kernels write into, the device-resident lr / step counter
+    and the checkpoint surface shared by every rule.  A rule names its flat fp32 state arrays in STATE (allocated here,
+    zero-initialised, saved under those names) and launches its kernels in _launch."""
+    STATE = ()
+
+    def __init__(self, params, lr, weight_decay=0.0):
         seen, plist = set(), []
         for p in params:
             if p.requires_grad and id(p) not in seen:      # FusedUNet registers every stage twice
@@ -27,8 +33,8 @@ class FlatAdamW:
         self.offsets, self.total = offs, total
         self.flat_p = torch.zeros(total, dtype=torch.float32, device=dev)
         self.flat_g = torch.zeros(total, dtype=torch.float32, device=dev)
-        self.exp_avg = torch.zeros(total, dtype=torch.float32, device=dev)
-        self.exp_avg_sq = torch.zeros(total, dtype=torch.float32, device=dev)
+        for name in self.STATE:
+            setattr(self, name, torch.zeros(total, dtype=torch.float32, device=dev))
         with torch.no_grad():
             for p, o in zip(plist, offs):
                 view = self.flat_p[o:o + p.numel()].view_as(p)
@@ -41,7 +47,7 @@ class FlatAdamW:
                 p._xv2_epoch = -1
         ops.clear_pack_cache()         # the parameters just moved to new storage
         self.epoch = 0
-        self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
+        self.lr, self.weight_decay = lr, weight_decay
         self.step_count = 0
         self.param_groups = [{"lr": lr, "params": plist}]  # what utils/scheduler.py NoamLR touches
         # device-resident copies for hipGraph capture (see xview2_amd.graph.GraphedStep)
@@ -74,6 +80,56 @@ class FlatAdamW:
             self._lr_on_dev = lr
 
     def step(self, grad_scale=1.0):
+        """one update; grad_scale multiplies the gradient first (the reducer's 1/world)"""
+        ops.join_wgrad_stream()      # weight-gradient kernels run on a side stream (ops.ASYNC_WGRAD)
+        self._gather_foreign_grads()
+        self.step_count += 1
+        if not self.capturable:
+            raise RuntimeError("%s steps on the GPU only (HIP kernels; there is no CPU fallback)" % type(self).__name__)
+        self.sync_lr()
+        self._launch(float(grad_scale))
+        ops.weights_changed()
+        ops.repack_all()       # the packed conv-weight layouts, refreshed in one launch
+
+    def _launch(self, grad_scale):
+        raise NotImplementedError
+
+    def _extra_state(self):
+        """state beyond the step, the flat STATE arrays and the lr (per-rule tensors / hyperparameters)"""
+        return {}
+
+    def _load_extra_state(self, sd):
+        pass
+
+    def state_dict(self):
+        sd = {"step": self.step_count}
+        sd.update((name, getattr(self, name)) for name in self.STATE)
+        sd.update(self._extra_state())
+        sd["lr"] = self.param_groups[0]["lr"]
+        return sd
+
+    def load_state_dict(self, sd):
+        self.step_count = sd["step"]
+        for name in self.STATE:
+            getattr(self, name).copy_(sd[name])
+        self._load_extra_state(sd)
+        self.param_groups[0]["lr"] = sd["lr"]
+        if self.step_dev is not None:
+            # the GPU kernels take their bias corrections from the device-resident counter
+            self.step_dev.fill_(int(sd["step"]))
+            self.sync_lr()
+
+
+class FlatAdamW(FlatOptimizer):
+    """model/plt.py:154 torch.optim.AdamW (and model/plt.py:153 apex FusedAdam, whose default adam_w_mode is the same
+    decoupled-decay update): one launch of xv2_adamw_step_dev"""
+    STATE = ("exp_avg", "exp_avg_sq")
+
+    def __init__(self, params, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+        super().__init__(params, lr, weight_decay)
+        self.betas, self.eps = betas, eps
+
+    def step(self, grad_scale=1.0):
         ops.join_wgrad_stream()      # weight-gradient kernels run on a side stream (ops.ASYNC_WGRAD)
         self._gather_foreign_grads()
         self.step_count += 1
@@ -91,16 +147,137 @@ class FlatAdamW:
                        self.eps, self.weight_decay, self.step_count, grad_scale)
         ops.weights_changed()
 
-    def state_dict(self):
-        return {"step": self.step_count, "exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq,
-                "lr": self.param_groups[0]["lr"]}
 
-    def load_state_dict(self, sd):
-        self.step_count = sd["step"]
-        self.exp_avg.copy_(sd["exp_avg"])
-        self.exp_avg_sq.copy_(sd["exp_avg_sq"])
-        self.param_groups[0]["lr"] = sd["lr"]
-        if self.step_dev is not None:
-            # the GPU kernel takes its bias correction from the device-resident counter
-            self.step_dev.fill_(int(sd["step"]))
-            self.sync_lr()
+class _FlatRule(FlatOptimizer):
+    """a rule of xv2_flat_step_dev: one elementwise launch over the flat buffer and up to two state arrays"""
+    RULE = None
+    betas, eps, momentum, final_lr, gamma = (0.9, 0.999), 1e-8, 0.0, 0.1, 1e-3
+
+    def _state_args(self):
+        return [getattr(self, name) for name in self.STATE] + [None] * (2 - len(self.STATE))
+
+    def _launch(self, grad_scale):
+        from ._capi import call
+        call("xv2_flat_step_dev", self.RULE, self.flat_p, self.flat_g, *self._state_args(), self.flat_p.numel(),
+             self.lr_dev, self.step_dev, float(self.betas[0]), float(self.betas[1]), float(self.eps),
+             float(self.weight_decay), float(self.momentum), float(getattr(self, "base_lr", 0.0)), float(self.final_lr),
+             float(self.gamma), grad_scale)
+
+
+class FlatSGD(_FlatRule):
+    """model/plt.py:152 apex FusedSGD(lr, momentum): dampening 0, no Nesterov, no weight decay (the reference passes
+    none, so --weight_decay does not reach it).  The momentum buffer starts as the first gradient."""
+
+    def __init__(self, params, lr=3e-4, momentum=0.0):
+        self.STATE = ("momentum_buffer",) if momentum != 0.0 else ()
+        super().__init__(params, lr, 0.0)
+        self.momentum = momentum
+        self.RULE = 1 if momentum != 0.0 else 0
+
+
+class FlatRAdam(_FlatRule):
+    """model/plt.py:155 torch_optimizer RAdam(lr, weight_decay): decoupled decay p *= 1 - lr * wd, the rectified Adam
+    step once rho_t >= 5, the bias-corrected momentum step before"""
+    RULE = 2
+    STATE = ("exp_avg", "exp_avg_sq")
+
+
+class FlatAdaBelief(_FlatRule):
+    """model/plt.py:156 torch_optimizer AdaBelief(lr, weight_decay): eps 1e-3 (the package's default), L2 decay added to
+    the gradient, eps accumulated into the variance state"""
+    RULE = 3
+    STATE = ("exp_avg", "exp_avg_var")
+    eps = 1e-3
+
+
+class FlatAdaBound(_FlatRule):
+    """model/plt.py:157 torch_optimizer AdaBound(lr, weight_decay): final_lr 0.1, gamma 1e-3, L2 decay; the bounds follow
+    the learning rate relative to base_lr (the rate at construction)"""
+    RULE = 4
+    STATE = ("exp_avg", "exp_avg_sq")
+
+    def __init__(self, params, lr=3e-4, weight_decay=0.0):
+        super().__init__(params, lr, weight_decay)
+        self.base_lr = lr
+
+    def _extra_state(self):
+        return {"base_lr": self.base_lr}
+
+    def _load_extra_state(self, sd):
+        self.base_lr = sd["base_lr"]
+
+
+class _FlatSegmented(FlatOptimizer):
+    """rules with per-tensor / per-output-channel sums: the segment table of include/xv2.h (rows = dim-0 slices of a
+    tensor with >= 2 dims, else the whole tensor) and the scratch, built once here"""
+    betas, eps = (0.9, 0.999), 1e-8
+
+    def __init__(self, params, lr, weight_decay):
+        super().__init__(params, lr, weight_decay)
+        rows, tens = [], []
+        for i, (p, o) in enumerate(zip(self.params, self.offsets)):
+            n = p.numel()
+            nr = p.shape[0] if p.dim() >= 2 and n > 0 else 1
+            ln = n // nr
+            tens.append((len(rows), nr, n, int(p.dim() >= 2)))
+            rows.extend((o + r * ln, ln, i) for r in range(nr))
+        dev = self.flat_p.device
+        self.rows = torch.tensor(rows, dtype=torch.int64, device=dev)
+        self.tensors = torch.tensor(tens, dtype=torch.int64, device=dev)
+        self.partials = torch.zeros(len(rows), 4, dtype=torch.float32, device=dev)
+
+
+class FlatAdamP(_FlatSegmented):
+    """model/plt.py:158 torch_optimizer AdamP(lr, weight_decay): delta 0.1, wd_ratio 0.1.  `decision` holds the view the
+    last step projected each tensor with (0 none, 1 channel, 2 layer)."""
+    STATE = ("exp_avg", "exp_avg_sq")
+    delta, wd_ratio = 0.1, 0.1
+
+    def __init__(self, params, lr=3e-4, weight_decay=0.0):
+        super().__init__(params, lr, weight_decay)
+        dev = self.flat_p.device
+        self.decision = torch.zeros(len(self.params), dtype=torch.int32, device=dev)
+        self.aux = torch.zeros(len(self.params), 2, dtype=torch.float32, device=dev)
+
+    def _launch(self, grad_scale):
+        from ._capi import call
+        call("xv2_adamp_step_dev", self.rows, self.rows.shape[0], self.tensors, len(self.params), self.flat_p,
+             self.flat_g, self.exp_avg, self.exp_avg_sq, self.partials, self.decision, self.aux, self.lr_dev,
+             self.step_dev, float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.weight_decay),
+             float(self.delta), float(self.wd_ratio), grad_scale)
+
+
+class FlatNovoGrad(_FlatSegmented):
+    """model/plt.py:159 apex FusedNovoGrad(lr, weight_decay): grad averaging and bias correction on, decay outside the
+    moment, L2 norms; exp_avg_norm is the per-tensor blended gradient norm (the first step's norm at step 1)"""
+    STATE = ("exp_avg",)
+
+    def __init__(self, params, lr=3e-4, weight_decay=0.0):
+        super().__init__(params, lr, weight_decay)
+        self.exp_avg_norm = torch.zeros(len(self.params), dtype=torch.float32, device=self.flat_p.device)
+
+    def _extra_state(self):
+        return {"exp_avg_norm": self.exp_avg_norm}
+
+    def _load_extra_state(self, sd):
+        self.exp_avg_norm.copy_(sd["exp_avg_norm"])
+
+    def _launch(self, grad_scale):
+        from ._capi import call
+        call("xv2_novograd_step_dev", self.rows, self.rows.shape[0], self.tensors, len(self.params), self.flat_p,
+             self.flat_g, self.exp_avg, self.exp_avg_norm, self.partials, self.lr_dev, self.step_dev,
+             float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.weight_decay), grad_scale)
+
+
+def make_flat_optimizer(name, params, lr, weight_decay=0.0, momentum=0.0):
+    """the flat optimizer of one --optimizer choice, with the hyperparameters model/plt.py:150-161 passes"""
+    name = name.lower()
+    if name == "sgd":
+        return FlatSGD(params, lr=lr, momentum=momentum)
+    if name in ("adam", "adamw"):
+        return FlatAdamW(params, lr=lr, weight_decay=weight_decay)
+    rules = {"radam": FlatRAdam, "adabelief": FlatAdaBelief, "adabound": FlatAdaBound, "adamp": FlatAdamP,
+             "novograd": FlatNovoGrad}
+    if name not in rules:
+        raise ValueError("unknown optimizer %r (choices: sgd, adam, adamw, %s)" % (name, ", ".join(rules)))
+    return rules[name](params, lr=lr, weight_decay=weight_decay)

@@ -11,7 +11,7 @@ import os
 import torch
 
 from . import dist as xdist
-from .optim import FlatAdamW
+from .optim import FlatOptimizer
 
 
 class Trainer:
@@ -40,7 +40,7 @@ class Trainer:
         os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
         ckpt = {"state_dict": {k: v.detach().cpu() for k, v in model.state_dict().items()},
                 "hyper_parameters": {"args": model.args}, "epoch": epoch, "global_step": self.global_step}
-        if isinstance(optimizer, FlatAdamW):
+        if isinstance(optimizer, FlatOptimizer):
             ckpt["optimizer_states"] = [{k: (v.cpu() if torch.is_tensor(v) else v)
                                          for k, v in optimizer.state_dict().items()}]
         torch.save(ckpt, path)
@@ -65,15 +65,15 @@ class Trainer:
             model.load_state_dict(ckpt["state_dict"])
             start_epoch = ckpt.get("epoch", -1) + 1
             self.global_step = ckpt.get("global_step", 0)
-            if isinstance(optimizer, FlatAdamW) and ckpt.get("optimizer_states"):
+            if isinstance(optimizer, FlatOptimizer) and ckpt.get("optimizer_states"):
                 st = ckpt["optimizer_states"][0]
                 optimizer.load_state_dict({k: (v.to(self.device) if torch.is_tensor(v) else v) for k, v in st.items()})
             if scheduler is not None:
                 # NoamLR counts from 1 (its constructor steps once): after n optimizer steps it stands at n + 1
                 scheduler.step(self.global_step + 1)
-                if isinstance(optimizer, FlatAdamW):
+                if isinstance(optimizer, FlatOptimizer):
                     optimizer.sync_lr()
-        flat = isinstance(optimizer, FlatAdamW)
+        flat = isinstance(optimizer, FlatOptimizer)
         reducer = xdist.GradReducer(optimizer, sync_bn=self.sync_batchnorm or self.world > 1) if flat else None
         frozen = False
         for epoch in range(start_epoch, self.max_epochs):

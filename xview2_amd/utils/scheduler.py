@@ -1,7 +1,7 @@
 """Noam learning-rate schedule (linear warm-up, exponential decay), stepped once per optimizer step.
 Host-side scalar arithmetic with the constructor contract of the reference's utils/scheduler.py:6-59
 (warmup_epochs, total_epochs, steps_per_epoch, init_lr, max_lr, final_lr); works with any optimizer object
-exposing ``param_groups`` (torch.optim.* or xview2_amd.optim.FlatAdamW)."""
+exposing ``param_groups`` (torch.optim.* or a xview2_amd.optim.FlatOptimizer)."""
 
 
 class NoamLR:
