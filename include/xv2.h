@@ -601,6 +601,36 @@ int xv2_xchg_free(void* base);
 int xv2_xchg_allreduce(double* vals, int n, const void* peers_dev, int world, int rank, size_t row_doubles,
                        uint64_t seq, int* timeout_flag, void* stream);
 
+/* ---- offline post-processing and scoring (utils/post_process.py, utils/xview2_metrics.py) ---------------------------
+ * Batches of B tiles of H x W, row-major.  Connected-component labels: 1 + the smallest in-tile linear index
+ * (y * W + x) of the pixel's 4-connected component, 0 = background (np.unique(labels, return_inverse=True) gives
+ * scipy.ndimage.label's numbering). */
+#define XV2_DMG_4CH 0    /* fp32 [B,4,H,W] damage probabilities: post = argmax + 1 (post_process.py:31-32) */
+#define XV2_DMG_5CH 1    /* fp32 [B,5,H,W] background + 4 damage channels: argmax over channels 1..4, + 1 */
+#define XV2_DMG_LABEL 2  /* int32 [B,H,W] decoded label map (coral / mse: post_process.py:33-34) */
+/* Workspace bytes of xv2_postprocess: 22 per pixel with components (counts, labels, pre / post intermediates), 2
+ * without (used only when dilating).  Nothing in it needs clearing by the caller. */
+size_t xv2_postprocess_workspace(int B, int H, int W, int components);
+/* post_process.py:28-44: pre = (loc > 0.3f) | ((loc > 0.1f) & (post > 1)) in float32, post *= pre; components != 0:
+ * every pixel of a 4-connected component of post > 0 takes the component's most frequent post value (ties: the smaller,
+ * post_process.py:40-43); rate > 0 (odd, <= 65): both maps dilated by a rate x rate square clamped to the image
+ * (post_process.py:44-45); uint8 [B,H,W] pre and post out.  An even rate, another dmg_kind or a non-positive size is
+ * XV2_EINVAL.  workspace may be NULL when components == 0 and rate == 0.
+ * Label maps: any int32 value is read; only the values that survive the fusion (pre set) must be representable:
+ * 0..255 (the uint8 PNG), or 0..4 with components (the vote keeps four classes per component).  A surviving value outside
+ * that range is written as background and counted into *status (device int32, accumulated, never cleared; required for
+ * XV2_DMG_LABEL, may be NULL otherwise), so the caller can reject the result. */
+int xv2_postprocess(const float* loc, const void* dmg, int dmg_kind, int B, int H, int W, int components, int rate,
+                    void* workspace, uint8_t* pre, uint8_t* post, int32_t* status, void* stream);
+/* scipy.ndimage.label of mask != 0 (post_process.py:39) with the labels above, int32 [B,H,W] out.  workspace is
+ * unused (may be NULL); labels is the union-find's own storage. */
+int xv2_label_components(const uint8_t* mask, int B, int H, int W, void* workspace, int32_t* labels, void* stream);
+/* xview2_metrics.py RowPairCalculator.get_row_pair over four uint8 [B,hw] maps: counts[b*16 + ...] += [lTP, lFN, lFP],
+ * [TP, FN, FP] x damage classes 1..4, then the number of pixels holding a value > 4 in any map.  `counts` (int64,
+ * device) is accumulated into, never cleared. */
+int xv2_xview2_counts(const uint8_t* lp, const uint8_t* dp, const uint8_t* lt, const uint8_t* dt, int B, int64_t hw,
+                      int64_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2070,3 +2070,89 @@ def f1_counts(pred_u8, target_u8, n_class, masked, counts):
 def adamw_step(p, g, m, v, lr, beta1, beta2, eps, wd, step, grad_scale=1.0):
     call("xv2_adamw_step", p, g, m, v, p.numel(), float(lr), float(beta1), float(beta2), float(eps), float(wd),
          int(step), float(grad_scale))
+
+
+# ---- offline post-processing and scoring (csrc/postproc.hip) -------------------------------------------------------
+def postprocess_workspace(B, H, W, components, device):
+    """uint8 workspace of xv2_postprocess from torch's caching allocator (a caller running many batches may keep it)"""
+    n = query("xv2_postprocess_workspace", int(B), int(H), int(W), 1 if components else 0)
+    return torch.empty(max(int(n), 1), dtype=torch.uint8, device=device)
+
+
+def postprocess(loc, dmg, components=False, rate=0, workspace=None):
+    """utils/post_process.py:28-45 on a batch: loc fp32 [B,H,W]; dmg fp32 [B,4|5,H,W] probabilities or a [B,H,W]
+    label map (any integer or float dtype, converted to int32 on the device).  Label-map values that survive the fusion
+    must be representable: 0..255 (uint8 output), 0..4 with components; anything else raises ValueError (the kernel
+    counts such pixels; values dropped by the fusion, e.g. an unclamped mse decode on background, are not checked).
+    rate = 0: no dilation, else an odd square edge.  workspace: None or a uint8 CUDA tensor of at least
+    postprocess_workspace() bytes, 256-byte aligned.  Returns uint8 (pre, post), [B,H,W] each."""
+    _need_cuda(loc)
+    _need_cuda(dmg)
+    if loc.dim() != 3:
+        raise ValueError("postprocess: loc must be [B,H,W], got %s" % (tuple(loc.shape),))
+    B, H, W = loc.shape
+    loc = loc.contiguous().float()
+    status = None
+    if dmg.dim() == 4:
+        if tuple(dmg.shape) not in ((B, 4, H, W), (B, 5, H, W)):
+            raise ValueError("postprocess: damage probabilities must be [B,4|5,H,W] matching loc %s, got %s"
+                             % (tuple(loc.shape), tuple(dmg.shape)))
+        kind = 0 if dmg.shape[1] == 4 else 1
+        dmg = dmg.contiguous().float()
+    elif dmg.dim() == 3 and tuple(dmg.shape) == (B, H, W):
+        kind = 2
+        dmg = dmg.to(torch.int32).contiguous()
+        status = torch.zeros(1, dtype=torch.int32, device=loc.device)
+    else:
+        raise ValueError("postprocess: dmg %s fits neither [B,4|5,H,W] nor [B,H,W] for loc %s"
+                         % (tuple(dmg.shape), tuple(loc.shape)))
+    rate = int(rate)
+    if rate and rate % 2 == 0:
+        raise ValueError("postprocess: dilation rate must be odd, got %d" % rate)
+    if components or rate:
+        need = int(query("xv2_postprocess_workspace", int(B), int(H), int(W), 1 if components else 0))
+        if workspace is None:
+            workspace = postprocess_workspace(B, H, W, components, loc.device)
+        elif (workspace.dtype != torch.uint8 or workspace.device != loc.device or not workspace.is_contiguous()
+              or workspace.numel() < need or workspace.data_ptr() % 256):
+            raise ValueError("postprocess: workspace must be a contiguous uint8 tensor on %s of at least %d bytes, "
+                             "256-byte aligned (got %s %s, %d bytes)" % (loc.device, need, workspace.dtype,
+                                                                         workspace.device, workspace.numel()))
+    pre = torch.empty((B, H, W), dtype=torch.uint8, device=loc.device)
+    post = torch.empty_like(pre)
+    call("xv2_postprocess", loc, dmg, kind, B, H, W, 1 if components else 0, rate, workspace, pre, post, status)
+    if status is not None:
+        bad = int(status.item())
+        if bad:
+            raise ValueError("postprocess: %d predicted pixels hold a damage label outside %s; the label map must be "
+                             "clamped first" % (bad, "1..4 (--components votes over four classes)" if components
+                                                else "0..255"))
+    return pre, post
+
+
+def label_components(mask):
+    """4-connected components of mask != 0 over [B,H,W] (uint8 or bool): int32 labels, 1 + the smallest linear index
+    of the component within its tile, 0 for background"""
+    _need_cuda(mask)
+    if mask.dim() != 3:
+        raise ValueError("label_components: mask must be [B,H,W], got %s" % (tuple(mask.shape),))
+    mask = mask.to(torch.uint8).contiguous()
+    B, H, W = mask.shape
+    labels = torch.empty((B, H, W), dtype=torch.int32, device=mask.device)
+    call("xv2_label_components", mask, B, H, W, None, labels)
+    return labels
+
+
+def xview2_counts(lp, dp, lt, dt):
+    """int64 [B,16] per-tile scorer rows over four uint8 [B,...] maps (include/xv2.h xv2_xview2_counts)"""
+    maps = []
+    for t in (lp, dp, lt, dt):
+        _need_cuda(t)
+        if t.dtype != torch.uint8 or t.shape != lp.shape:
+            raise ValueError("xview2_counts: four uint8 maps of one shape expected")
+        maps.append(t.contiguous())
+    B = lp.shape[0]
+    hw = lp[0].numel()
+    counts = torch.zeros((B, 16), dtype=torch.int64, device=lp.device)
+    call("xv2_xview2_counts", *maps, B, hw, counts)
+    return counts

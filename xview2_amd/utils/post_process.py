@@ -1,0 +1,153 @@
+"""Post-processing of the evaluation outputs (reference utils/post_process.py) on the MI355X.
+
+`main.py --exec_mode eval` writes probs/test_{localization,damage}_NNNNN.npy; this step fuses each pair, optionally
+replaces every predicted building's damage by its majority class (--components) and dilates both maps (--dilate), and
+writes predictions/test_{localization,damage}_NNNNN_prediction.png.  The work runs in the HIP kernels of
+csrc/postproc.hip (xv2_postprocess), a batch of tiles per launch sequence; there is no host path.
+
+Semantics are the reference's (post_process.py:27-47), bit for bit, with these deliberate departures:
+  1. five-channel damage probabilities (a softmax that carries a background channel first) use
+     post = argmax(dmg[1:5]) + 1: the background channel is dropped and the four-channel rule applies.  The reference
+     raises IndexError on this input.  Four-channel input and label maps behave as in the reference;
+  2. the dilation rate must be odd (>= 1): an even rate raises ValueError (skimage's centring of even footprints has
+     changed between releases);
+  3. tiles of any H x W are accepted (the reference hard-codes 1024 x 1024);
+  4. the CLI takes --results DIR (default /results, the reference's fixed root) and --batch N;
+  5. label maps (coral / mse decodes) are converted to int32.  Values dropped by the fusion are never looked at, so
+     an unclamped mse decode on background behaves as in the reference.  A value that survives it must fit the
+     output: 0..255 without --components, 1..4 with it (the vote keeps four classes per building); otherwise
+     ValueError, where the reference would vote over it and write a PNG its scorer rejects.
+
+    python -m xview2_amd.utils.post_process --results R [--components] [--dilate [--dilation_rate 3]]
+"""
+import os
+from argparse import ArgumentDefaultsHelpFormatter, ArgumentParser, ArgumentTypeError
+from concurrent.futures import ThreadPoolExecutor
+from glob import glob
+
+import numpy as np
+import torch
+
+from .. import ops
+
+
+def _check_rate(dilate, dilation_rate):
+    if not dilate:
+        return 0
+    r = int(dilation_rate)
+    if r < 1 or r % 2 == 0:
+        raise ValueError("dilation_rate must be odd and >= 1, got %d" % r)
+    return r
+
+
+def post_process_tiles(loc, dmg, components=False, dilate=False, dilation_rate=3, workspace=None):
+    """uint8 (pre, post) on the device.  loc: fp32 [H,W] or [B,H,W]; dmg: [4|5,H,W] / [B,4|5,H,W] probabilities or an
+    [H,W] / [B,H,W] label map.  Unbatched input gives unbatched output."""
+    rate = _check_rate(dilate, dilation_rate)
+    single = loc.dim() == 2
+    if single:
+        loc, dmg = loc.unsqueeze(0), dmg.unsqueeze(0)
+    pre, post = ops.postprocess(loc, dmg, components=components, rate=rate, workspace=workspace)
+    return (pre[0], post[0]) if single else (pre, post)
+
+
+def connected_components(mask):
+    """int32 labels of the 4-connected components of mask != 0 ([H,W] or [B,H,W], on the device): 1 + the smallest
+    linear index of the component within its tile, 0 for background.  np.unique(labels, return_inverse=True) gives
+    scipy.ndimage.label's numbering."""
+    single = mask.dim() == 2
+    lab = ops.label_components(mask.unsqueeze(0) if single else mask)
+    return lab[0] if single else lab
+
+
+def _device():
+    if not torch.cuda.is_available():
+        raise RuntimeError("xview2_amd.utils.post_process runs on the MI355X only; there is no CPU fallback")
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _to_device(a, dev):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(dev, non_blocking=False)
+
+
+def _save(img, path):
+    from PIL import Image
+    Image.fromarray(img).save(path)
+
+
+def _out_name(path):
+    return os.path.basename(path).replace(".npy", "_prediction.png")
+
+
+def post_process(args, pre_path, post_path):
+    """one pair of .npy files -> two prediction PNGs under <args.results>/predictions (reference signature)"""
+    results = getattr(args, "results", "/results")
+    dev = _device()
+    loc, dmg = _to_device(np.load(pre_path), dev), _to_device(np.load(post_path), dev)
+    pre, post = post_process_tiles(loc, dmg, args.components, args.dilate, args.dilation_rate)
+    _save(pre.cpu().numpy(), os.path.join(results, "predictions", _out_name(pre_path)))
+    _save(post.cpu().numpy(), os.path.join(results, "predictions", _out_name(post_path)))
+
+
+def run(args):
+    """the CLI: every probs/*localization* with its probs/*damage* partner (sorted pairing, as the reference), --batch
+    pairs per GPU call, PNGs written from a small thread pool"""
+    rate = _check_rate(args.dilate, args.dilation_rate)
+    if args.batch < 1:
+        raise ValueError("--batch must be >= 1, got %d" % args.batch)
+    pred_dir = os.path.join(args.results, "predictions")
+    os.makedirs(pred_dir, exist_ok=True)
+    pre_paths = sorted(glob(os.path.join(args.results, "probs", "*localization*")))
+    post_paths = sorted(glob(os.path.join(args.results, "probs", "*damage*")))
+    if len(pre_paths) != len(post_paths):
+        raise ValueError("%d localization files but %d damage files" % (len(pre_paths), len(post_paths)))
+    dev = _device()
+    workspace = {}
+    with ThreadPoolExecutor(max_workers=4) as pool:
+        pending = []
+        for i in range(0, len(pre_paths), args.batch):
+            pairs = list(zip(pre_paths[i:i + args.batch], post_paths[i:i + args.batch]))
+            locs = [np.load(a) for a, _ in pairs]
+            dmgs = [np.load(b) for _, b in pairs]
+            groups = {}
+            for k, (l, d) in enumerate(zip(locs, dmgs)):   # one launch per input geometry
+                groups.setdefault((l.shape, d.shape, d.dtype.str), []).append(k)
+            for (lshape, _, _), ks in groups.items():
+                loc = _to_device(np.stack([locs[k] for k in ks]), dev)
+                dmg = _to_device(np.stack([dmgs[k] for k in ks]), dev)
+                key = (len(ks),) + tuple(lshape)
+                if key not in workspace and (args.components or rate):
+                    workspace[key] = ops.postprocess_workspace(len(ks), lshape[0], lshape[1], args.components, dev)
+                pre, post = ops.postprocess(loc, dmg, components=args.components, rate=rate,
+                                            workspace=workspace.get(key))
+                pre, post = pre.cpu().numpy(), post.cpu().numpy()
+                for j, k in enumerate(ks):
+                    a, b = pairs[k]
+                    pending.append(pool.submit(_save, pre[j], os.path.join(pred_dir, _out_name(a))))
+                    pending.append(pool.submit(_save, post[j], os.path.join(pred_dir, _out_name(b))))
+        for f in pending:
+            f.result()
+    return len(pre_paths)
+
+
+def _positive_int(text):
+    v = int(text)
+    if v < 1:
+        raise ArgumentTypeError("must be >= 1, got %d" % v)
+    return v
+
+
+def get_parser():
+    parser = ArgumentParser(formatter_class=ArgumentDefaultsHelpFormatter)
+    arg = parser.add_argument
+    arg("--components", action="store_true", help="Enable connected component analysis for post disaster")
+    arg("--dilate", action="store_true", help="Dilate pre and post images")
+    arg("--dilation_rate", type=int, default=3, help="Dilation rate (odd)")
+    arg("--results", type=str, default="/results", help="Directory holding probs/; predictions/ is written there")
+    arg("--batch", type=_positive_int, default=8, help="Tiles per GPU call")
+    return parser
+
+
+if __name__ == "__main__":
+    n = run(get_parser().parse_args())
+    print("post-processed %d tile pairs" % n)
