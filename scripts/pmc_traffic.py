@@ -50,18 +50,17 @@ def pretty(mangled):
                "wgrad_reduce_kernel", "splitk_reduce_kernel", "adamw_dev_kernel", "stem7x7_kernel", "stem7x7_wgrad_kernel"):
         if nm in mangled:
             return nm
-    m = re.match(r"_ZN3xv2\d+(igemm|wgrad)_kernelI(.*?)EEv", mangled)
+    m = re.match(r"_ZN3xv2\d+igemm_kernelILNS_4FormE(\d+)ELi(\d+)ELi(\d+)EEEv", mangled)
+    if m:      # enum Form of igemm_kernel.h, in its order -> the suffix of FORM_TRAITS there
+        form, bm, bn = (int(v) for v in m.groups())
+        tag = ("rgb", "rgb,bf16out", "c32", "c32,bf16", "c32,bf16hbm", "c32,bf16hbm,halo", "c32,f32x3", "c32,f32x3,halo",
+               "c32,f32x3,halo,wx3", "c32,f16x2", "c32,f16x2,halo,wx2")[form]
+        return "igemm_kernel<%d,%d,%d,%d,%s>" % (bm, bn, 4 if bn == 32 else 2, 1 if bn == 32 else 2, tag)
+    m = re.match(r"_ZN3xv2\d+wgrad_kernelI(.*?)EEv", mangled)
     if not m:
         return None
-    args = re.findall(r"L([ib])(\d+)E", m.group(2))
+    args = re.findall(r"L([ib])(\d+)E", m.group(1))
     vals = [int(v) for _, v in args] + [0, 0, 0, 0, 0, 0, 0]
-    if m.group(1) == "igemm":
-        smallc, bf16, hs, x3, halo, bx3, npl = vals[4], vals[5], vals[6], vals[7], vals[8], vals[9], vals[10]
-        x3tag = (("c32,f16x2" + (",halo" if halo else "") + (",wx2" if bx3 else "")) if npl == 2 else
-                 ("c32,f32x3" + (",halo" if halo else "") + (",wx3" if bx3 else "")))
-        tag = ("rgb,bf16out" if hs else "rgb") if smallc else (
-            "c32,bf16hbm" if hs else (x3tag if x3 else ("c32,bf16" if bf16 else "c32")))
-        return "igemm_kernel<%d,%d,%d,%d,%s>" % (vals[0], vals[1], vals[2], vals[3], tag)
     smallc, bf16, hs = vals[5], vals[6], vals[7]
     tag = ("rgb" if smallc else ("c32,bf16" if bf16 else "c32")) + (",bf16hbm" if hs else "")
     return "wgrad_kernel<%d,%d,%d,%d,%d,%s>" % (vals[0], vals[1], vals[2], vals[3], vals[4], tag)

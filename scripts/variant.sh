@@ -1,6 +1,6 @@
 #!/bin/bash
 # build a variant of the library with extra compiler flags for ONE source (A/B runs on the same box):
-#   scripts/variant.sh NAME SOURCE.hip "-DXV2_PF=3 ..."   ->  xview2_amd/abl/xv2_NAME.so   (use with XV2_LIB=...)
+#   scripts/variant.sh NAME SOURCE.hip "-DXV2_HABL=16 ..."   ->  xview2_amd/abl/xv2_NAME.so   (use with XV2_LIB=...)
 cd $(dirname $0)/../xview2_amd
 NAME=$1; SRC=$2; FLAGS=$3
 BASE=$(basename $SRC .hip)

@@ -150,7 +150,7 @@ def test_cfg2_conv_layer_at_true_size(case):
         assert not any("f16x2" in n for n in runs[False]["names"]), runs[False]["names"]
         if k == 3 and s == 1 and Cout % 64 == 0 and (C1 or B * H * H > 40000):
             # 3x3 / stride 1 above the small-grid kernel's range (or with two sources): forward AND backward-data take the halo
-            # form with pre-split weights - since round 6 its K loop is the straight-line code of igemm_conv.hip (XV2_HU)
+            # form with pre-split weights - since round 6 its K loop is the straight-line code of igemm_kernel.h
             halo = [n for n in conv_names if n.startswith("igemm_kernel") and "halo,wx2" in n]
             assert len(halo) >= 2, conv_names
     # host reference

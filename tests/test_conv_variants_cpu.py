@@ -117,7 +117,11 @@ def test_bf16_storage_gate_takes_the_output_rounding_and_nothing_more():
 
 # ---- the variant table is complete ------------------------------------------------------------------------------------
 
-_MACROS = ("XV2_THIN_CASE", "XV2_SG_CASE")      # macros whose expansions launch kernels (thin_conv.hip, sg_conv.hip)
+_MACROS = ("XV2_IGEMM_TILES", "XV2_THIN_CASE", "XV2_SG_CASE")      # macros whose expansions launch kernels (igemm_conv.hip, thin_conv.hip, sg_conv.hip)
+# enum Form of igemm_kernel.h -> the form's part of the registered name (restating FORM_TRAITS there)
+_IGEMM_FORMS = {"RGB": "rgb", "RGB_BF16OUT": "rgb,bf16out", "C32": "c32", "BF16": "c32,bf16", "BF16HBM": "c32,bf16hbm",
+                "BF16HBM_HALO": "c32,bf16hbm,halo", "F32X3": "c32,f32x3", "F32X3_HALO": "c32,f32x3,halo",
+                "F32X3_HALO_WX3": "c32,f32x3,halo,wx3", "F16X2": "c32,f16x2", "F16X2_HALO": "c32,f16x2,halo,wx2"}
 
 
 def expand_launch_macros(t):
@@ -169,20 +173,9 @@ def registered_name(key):
     a = m.group(2).split(",")
     t = lambda i, dflt: (a[i] == "true") if i < len(a) else dflt
     if m.group(1) == "launch_one":
-        BM, BN, WGM, WGN = a[:4]
-        SMALLC, BF16, HS, X3, HALO, BX3 = t(4, False), t(5, False), t(6, False), t(7, False), t(8, False), t(9, False)
-        NPL = a[10] if len(a) > 10 else "3"
-        if SMALLC:
-            suffix = "rgb,bf16out" if HS else "rgb"
-        elif HS:
-            suffix = "c32,bf16hbm,halo" if HALO else "c32,bf16hbm"
-        elif X3 and HALO:
-            suffix = ("c32,f16x2,halo,wx2" if NPL == "2" else "c32,f32x3,halo,wx3") if BX3 else "c32,f32x3,halo"
-        elif X3:
-            suffix = "c32,f16x2" if NPL == "2" else "c32,f32x3"
-        else:
-            suffix = "c32,bf16" if BF16 else "c32"
-        return "igemm_kernel<%s,%s,%s,%s,%s>" % (BM, BN, WGM, WGN, suffix)
+        form, BM, BN = a
+        WGM, WGN = ("4", "1") if BN == "32" else ("2", "2")      # waves of a block along M x N: a function of the tile
+        return "igemm_kernel<%s,%s,%s,%s,%s>" % (BM, BN, WGM, WGN, _IGEMM_FORMS[form[len("Form::"):]])
     if m.group(1) == "sg_launch_one":
         WM, G, NB = (int(v) for v in a[:3])
         return "sg_conv_kernel<%d,%d,g%d,%s%s>" % (32 * WM, 32 * NB, G, "1x1," if t(3, False) else "", "bf16hbm" if t(4, False) else "f16x2")
@@ -203,11 +196,11 @@ def test_variant_table_lists_exactly_the_instantiations_of_the_conv_sources():
 def test_an_added_instantiation_is_caught():
     from tests.test_conv_variants_gpu import VARIANTS
     texts = _texts()
-    texts[0] += "\n    return launch_one<64, 32, 2, 2, false, true, false, true>(p, stream);\n"
+    texts[0] += "\n    return launch_one<Form::F32X3, 64, 32>(p, stream);\n"
     texts[3] = texts[3].replace("    XV2_THIN_CASE(64, 64)\n", "    XV2_THIN_CASE(64, 64)\n    XV2_THIN_CASE(32, 64)\n")
     texts[2] = texts[2].replace("        XV2_SG_CASE(242, 2, 4, 2)\n", "        XV2_SG_CASE(242, 2, 4, 2)\n        XV2_SG_CASE(222, 2, 2, 2)\n")
     added = set(source_variants(texts)) - set(VARIANTS)
-    assert added == {"launch_one<64,32,2,2,false,true,false,true>", "thin_launch_one<32,64,true,2,2>",
+    assert added == {"launch_one<Form::F32X3,64,32>", "thin_launch_one<32,64,true,2,2>",
                      "thin_launch_one<32,64,true,2,4>", "thin_launch_one<32,64,false,4,4,0,2>", "thin_launch_one<32,64,false,4,4>",
                      "sg_launch_one<2,2,2,true,true>", "sg_launch_one<2,2,2,false,true>", "sg_launch_one<2,2,2,true,false>",
                      "sg_launch_one<2,2,2,false,false>"}, sorted(added)

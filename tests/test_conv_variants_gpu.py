@@ -1,8 +1,8 @@
 """Every convolution kernel variant against a float64 reference, at the shapes, math modes and edges where kernels go wrong.
 
 VARIANTS names the kernel instantiations of the convolution sources that carry a profiler name of their own - each distinct
-launch_one<...> / launch_wgrad<...> / sg_launch_one<...> / thin_launch_one<...> template argument list (the XV2_SG_CASE and
-XV2_THIN_CASE macros expanded) and each prof_register("...") literal - with that name.  An instantiation that only an A/B
+launch_one<...> / launch_wgrad<...> / sg_launch_one<...> / thin_launch_one<...> template argument list (the XV2_IGEMM_TILES,
+XV2_SG_CASE and XV2_THIN_CASE macros expanded) and each prof_register("...") literal - with that name.  An instantiation that only an A/B
 switch reaches reads "ablation-only: XV2_<switch>".  tests/test_conv_variants_cpu.py keeps the table equal to the sources and
 checks that the cases below reach every other entry.  Not told apart: the device kernels launched under one prof_register
 name - the all-taps weight gradient's 64 x 64 and 32 x 32 tile forms (wgrad_alltaps64_* / wgrad_alltaps_*) and its three
@@ -37,45 +37,45 @@ RECORD = os.environ.get("XV2_VARIANTS_RECORD")
 
 VARIANTS = {
     # igemm_conv.hip igemm_launch: halo form (3x3 / stride 1 / same size), split-K, RGB, per-tap tiles per math mode
-    "launch_one<128,128,2,2,false,true,true,false,true>": "igemm_kernel<128,128,2,2,c32,bf16hbm,halo>",
-    "launch_one<128,64,2,2,false,true,true,false,true>": "igemm_kernel<128,64,2,2,c32,bf16hbm,halo>",
-    "launch_one<128,128,2,2,false,true,false,true,true,true,2>": "igemm_kernel<128,128,2,2,c32,f16x2,halo,wx2>",
-    "launch_one<128,64,2,2,false,true,false,true,true,true,2>": "igemm_kernel<128,64,2,2,c32,f16x2,halo,wx2>",
-    "launch_one<128,128,2,2,false,true,false,true,true,true>": "igemm_kernel<128,128,2,2,c32,f32x3,halo,wx3>",
-    "launch_one<128,64,2,2,false,true,false,true,true,true>": "igemm_kernel<128,64,2,2,c32,f32x3,halo,wx3>",
-    "launch_one<128,128,2,2,false,true,false,true,true>": "igemm_kernel<128,128,2,2,c32,f32x3,halo>",
-    "launch_one<128,64,2,2,false,true,false,true,true>": "igemm_kernel<128,64,2,2,c32,f32x3,halo>",
-    "launch_one<128,128,2,2,false,true,true>": "igemm_kernel<128,128,2,2,c32,bf16hbm>",
-    "launch_one<128,128,2,2,false,true,false,true,false,false,2>": "igemm_kernel<128,128,2,2,c32,f16x2>",
-    "launch_one<128,128,2,2,false,true,false,true>": "igemm_kernel<128,128,2,2,c32,f32x3>",
-    "launch_one<128,128,2,2,false,true>": "igemm_kernel<128,128,2,2,c32,bf16>",
-    "launch_one<128,128,2,2,false>": "igemm_kernel<128,128,2,2,c32>",
-    "launch_one<128,128,2,2,true,false,true>": "igemm_kernel<128,128,2,2,rgb,bf16out>",
-    "launch_one<128,64,2,2,true,false,true>": "igemm_kernel<128,64,2,2,rgb,bf16out>",
-    "launch_one<128,32,4,1,true,false,true>": "igemm_kernel<128,32,4,1,rgb,bf16out>",
-    "launch_one<128,128,2,2,true>": "igemm_kernel<128,128,2,2,rgb>",
-    "launch_one<128,64,2,2,true>": "igemm_kernel<128,64,2,2,rgb>",
-    "launch_one<128,32,4,1,true>": "igemm_kernel<128,32,4,1,rgb>",
-    "launch_one<64,128,2,2,false,true,true>": "igemm_kernel<64,128,2,2,c32,bf16hbm>",
-    "launch_one<128,64,2,2,false,true,true>": "igemm_kernel<128,64,2,2,c32,bf16hbm>",
-    "launch_one<64,64,2,2,false,true,true>": "igemm_kernel<64,64,2,2,c32,bf16hbm>",
-    "launch_one<128,32,4,1,false,true,true>": "igemm_kernel<128,32,4,1,c32,bf16hbm>",
-    "launch_one<64,128,2,2,false,true,false,true,false,false,2>": "igemm_kernel<64,128,2,2,c32,f16x2>",
-    "launch_one<128,64,2,2,false,true,false,true,false,false,2>": "igemm_kernel<128,64,2,2,c32,f16x2>",
-    "launch_one<64,64,2,2,false,true,false,true,false,false,2>": "igemm_kernel<64,64,2,2,c32,f16x2>",
-    "launch_one<128,32,4,1,false,true,false,true,false,false,2>": "igemm_kernel<128,32,4,1,c32,f16x2>",
-    "launch_one<64,128,2,2,false,true,false,true>": "igemm_kernel<64,128,2,2,c32,f32x3>",
-    "launch_one<128,64,2,2,false,true,false,true>": "igemm_kernel<128,64,2,2,c32,f32x3>",
-    "launch_one<64,64,2,2,false,true,false,true>": "igemm_kernel<64,64,2,2,c32,f32x3>",
-    "launch_one<128,32,4,1,false,true,false,true>": "igemm_kernel<128,32,4,1,c32,f32x3>",
-    "launch_one<64,128,2,2,false,true>": "igemm_kernel<64,128,2,2,c32,bf16>",
-    "launch_one<128,64,2,2,false,true>": "igemm_kernel<128,64,2,2,c32,bf16>",
-    "launch_one<64,64,2,2,false,true>": "igemm_kernel<64,64,2,2,c32,bf16>",
-    "launch_one<128,32,4,1,false,true>": "igemm_kernel<128,32,4,1,c32,bf16>",
-    "launch_one<64,128,2,2,false>": "igemm_kernel<64,128,2,2,c32>",
-    "launch_one<128,64,2,2,false>": "igemm_kernel<128,64,2,2,c32>",
-    "launch_one<64,64,2,2,false>": "igemm_kernel<64,64,2,2,c32>",
-    "launch_one<128,32,4,1,false>": "igemm_kernel<128,32,4,1,c32>",
+    "launch_one<Form::BF16HBM_HALO,128,128>": "igemm_kernel<128,128,2,2,c32,bf16hbm,halo>",
+    "launch_one<Form::BF16HBM_HALO,128,64>": "igemm_kernel<128,64,2,2,c32,bf16hbm,halo>",
+    "launch_one<Form::F16X2_HALO,128,128>": "igemm_kernel<128,128,2,2,c32,f16x2,halo,wx2>",
+    "launch_one<Form::F16X2_HALO,128,64>": "igemm_kernel<128,64,2,2,c32,f16x2,halo,wx2>",
+    "launch_one<Form::F32X3_HALO_WX3,128,128>": "igemm_kernel<128,128,2,2,c32,f32x3,halo,wx3>",
+    "launch_one<Form::F32X3_HALO_WX3,128,64>": "igemm_kernel<128,64,2,2,c32,f32x3,halo,wx3>",
+    "launch_one<Form::F32X3_HALO,128,128>": "igemm_kernel<128,128,2,2,c32,f32x3,halo>",
+    "launch_one<Form::F32X3_HALO,128,64>": "igemm_kernel<128,64,2,2,c32,f32x3,halo>",
+    "launch_one<Form::BF16HBM,128,128>": "igemm_kernel<128,128,2,2,c32,bf16hbm>",
+    "launch_one<Form::F16X2,128,128>": "igemm_kernel<128,128,2,2,c32,f16x2>",
+    "launch_one<Form::F32X3,128,128>": "igemm_kernel<128,128,2,2,c32,f32x3>",
+    "launch_one<Form::BF16,128,128>": "igemm_kernel<128,128,2,2,c32,bf16>",
+    "launch_one<Form::C32,128,128>": "igemm_kernel<128,128,2,2,c32>",
+    "launch_one<Form::RGB_BF16OUT,128,128>": "igemm_kernel<128,128,2,2,rgb,bf16out>",
+    "launch_one<Form::RGB_BF16OUT,128,64>": "igemm_kernel<128,64,2,2,rgb,bf16out>",
+    "launch_one<Form::RGB_BF16OUT,128,32>": "igemm_kernel<128,32,4,1,rgb,bf16out>",
+    "launch_one<Form::RGB,128,128>": "igemm_kernel<128,128,2,2,rgb>",
+    "launch_one<Form::RGB,128,64>": "igemm_kernel<128,64,2,2,rgb>",
+    "launch_one<Form::RGB,128,32>": "igemm_kernel<128,32,4,1,rgb>",
+    "launch_one<Form::BF16HBM,64,128>": "igemm_kernel<64,128,2,2,c32,bf16hbm>",
+    "launch_one<Form::BF16HBM,128,64>": "igemm_kernel<128,64,2,2,c32,bf16hbm>",
+    "launch_one<Form::BF16HBM,64,64>": "igemm_kernel<64,64,2,2,c32,bf16hbm>",
+    "launch_one<Form::BF16HBM,128,32>": "igemm_kernel<128,32,4,1,c32,bf16hbm>",
+    "launch_one<Form::F16X2,64,128>": "igemm_kernel<64,128,2,2,c32,f16x2>",
+    "launch_one<Form::F16X2,128,64>": "igemm_kernel<128,64,2,2,c32,f16x2>",
+    "launch_one<Form::F16X2,64,64>": "igemm_kernel<64,64,2,2,c32,f16x2>",
+    "launch_one<Form::F16X2,128,32>": "igemm_kernel<128,32,4,1,c32,f16x2>",
+    "launch_one<Form::F32X3,64,128>": "igemm_kernel<64,128,2,2,c32,f32x3>",
+    "launch_one<Form::F32X3,128,64>": "igemm_kernel<128,64,2,2,c32,f32x3>",
+    "launch_one<Form::F32X3,64,64>": "igemm_kernel<64,64,2,2,c32,f32x3>",
+    "launch_one<Form::F32X3,128,32>": "igemm_kernel<128,32,4,1,c32,f32x3>",
+    "launch_one<Form::BF16,64,128>": "igemm_kernel<64,128,2,2,c32,bf16>",
+    "launch_one<Form::BF16,128,64>": "igemm_kernel<128,64,2,2,c32,bf16>",
+    "launch_one<Form::BF16,64,64>": "igemm_kernel<64,64,2,2,c32,bf16>",
+    "launch_one<Form::BF16,128,32>": "igemm_kernel<128,32,4,1,c32,bf16>",
+    "launch_one<Form::C32,64,128>": "igemm_kernel<64,128,2,2,c32>",
+    "launch_one<Form::C32,128,64>": "igemm_kernel<128,64,2,2,c32>",
+    "launch_one<Form::C32,64,64>": "igemm_kernel<64,64,2,2,c32>",
+    "launch_one<Form::C32,128,32>": "igemm_kernel<128,32,4,1,c32>",
     # wgrad_conv.hip wgrad_impl: the tiled weight-gradient kernel (RGB, bf16 storage, bf16 operands, exact fp32)
     "launch_wgrad<64,64,2,2,1,true,true,true>": "wgrad_kernel<64,64,2,2,1,rgb,bf16hbm>",
     "launch_wgrad<32,64,1,2,2,true,true,true>": "wgrad_kernel<32,64,1,2,2,rgb,bf16hbm>",

@@ -18,12 +18,6 @@
 #ifndef XV2_WABL
 #define XV2_WABL 0      // timing ablations of wgrad_alltaps64_x3_kernel (results are garbage): 1 no MFMA, 2 no split + plane stores, 4 no global loads, 8 no fragment reads
 #endif
-#ifndef XV2_WTI
-#define XV2_WTI 1      // transpose-read weight gradients: running (image, row, column) of the next tile instead of two divisions per tile
-#endif
-#ifndef XV2_WPF
-#define XV2_WPF 1      // all-taps 64 x 64 F16X2 kernel: fragment reads one product ahead of the MFMAs (0: read, wait, multiply per product)
-#endif
 namespace xv2 {
 
 struct WTap {
@@ -373,11 +367,7 @@ __global__ void __launch_bounds__(256) wgrad_tr_kernel(const WgradParams p) {
     int t_n = (kt0 * 32) / ohw, t_oh = ((kt0 * 32) - t_n * ohw) / p.OW, t_ow0 = (kt0 * 32) - t_n * ohw - t_oh * p.OW;
     auto gload = [&](int kt) {      // a 32-pixel reduction tile lies inside one output row (OW % 32 == 0)
         const int mb = kt * 32;
-#if XV2_WTI
         const int n = t_n, oh = t_oh, ow0 = t_ow0;
-#else
-        const int n = mb / ohw, oh = (mb - n * ohw) / p.OW, ow0 = mb - n * ohw - oh * p.OW;
-#endif
         t_ow0 += 32;
         if (t_ow0 >= p.OW) {
             t_ow0 = 0;
@@ -530,11 +520,7 @@ __global__ void __launch_bounds__(256) wgrad_tr_x3_kernel(const WgradParams p) {
     int t_n = (kt0 * 32) / ohw, t_oh = ((kt0 * 32) - t_n * ohw) / p.OW, t_ow0 = (kt0 * 32) - t_n * ohw - t_oh * p.OW;
     auto gload_into = [&](int kt, i32x4 (&ra)[APASS], i32x4 (&rb)[BPASS]) {   // a 32-pixel tile lies inside one output row
         const int mb = kt * 32;
-#if XV2_WTI
         const int n = t_n, oh = t_oh, ow0 = t_ow0;
-#else
-        const int n = mb / ohw, oh = (mb - n * ohw) / p.OW, ow0 = mb - n * ohw - oh * p.OW;
-#endif
         t_ow0 += 32;
         if (t_ow0 >= p.OW) {
             t_ow0 = 0;
@@ -1316,7 +1302,6 @@ __global__ void __launch_bounds__(256, 2) wgrad_alltaps64_x3_kernel(const WgradP
         }
 #endif
         const bf16_t* ab = planes + buf * 32 * 64;
-#if XV2_WPF
         if constexpr (NPL == 2) {
             // software pipeline over the 18 (k-step, tap) products of a row step: the transpose reads of product i + 1 are
             // issued BEFORE the three MFMAs of product i (8 more VGPRs)
@@ -1355,12 +1340,11 @@ __global__ void __launch_bounds__(256, 2) wgrad_alltaps64_x3_kernel(const WgradP
                 __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);                                            // ... then the MFMAs
                 __builtin_amdgcn_sched_barrier(0);
             }
-        } else
-#endif
+        } else      // three bf16 planes: read, wait, multiply per product
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
             const int pa = 16 * ks + frow, ca = wa * 32 + fcol;
-            const bf16x8 ah = frag(ab, pa, ca), am = frag(ab + PL, pa, ca), al = NPL == 3 ? frag(ab + (NPL - 1) * PL, pa, ca) : ah;
+            const bf16x8 ah = frag(ab, pa, ca), am = frag(ab + PL, pa, ca), al = frag(ab + (NPL - 1) * PL, pa, ca);
 #pragma unroll
             for (int kh = 0; kh < 3; ++kh) {
                 const bf16_t* row = planes + 2 * 32 * 64 + ((r - 1 + kh + 4) & 3) * 34 * 64;      // input row r-1+kh
@@ -1369,13 +1353,6 @@ __global__ void __launch_bounds__(256, 2) wgrad_alltaps64_x3_kernel(const WgradP
                     const int t = kh * 3 + kw, pb = pa + kw, cb = wb * 32 + fcol;
                     const bf16x8 bh = frag(row, pb, cb), bm = frag(row + PL, pb, cb);
                     f32x16 c = acc[t];
-                    if constexpr (NPL == 2) {
-                        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, am), __builtin_bit_cast(f16x8, bh), c, 0, 0, 0);
-                        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, ah), __builtin_bit_cast(f16x8, bm), c, 0, 0, 0);
-                        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, ah), __builtin_bit_cast(f16x8, bh), c, 0, 0, 0);
-                        __builtin_amdgcn_sched_barrier(0);
-                        continue;
-                    }
                     const bf16x8 bl = frag(row + (NPL - 1) * PL, pb, cb);
 #if XV2_T0 == 0
                     c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, c, 0, 0, 0);
