@@ -355,6 +355,40 @@ int xv2_splat_tail_backward(const void* x, const void* dout, int N, int64_t hw, 
                             const float* att, int train, int parts, float* datt, float* dlogits, float* da1,
                             float* dh1, float* dgap, float* dw2, float* db2, float* dgamma1, float* dbeta1,
                             float* dw1, float* db1, void* dx, float* workspace, int dtype, void* stream);
+/* ---- head fusion: the <= 4-channel head of the last decoder layer inside that layer's BatchNorm passes ----
+ * The reference's last decoder ConvLayer (model/layers.py:89-100: conv -> norm -> LeakyReLU) feeds OutputBlock's 1x1 convolution
+ * (model/layers.py:171-189; model/unet.py:191-197 hands it dec5) and nothing else.  Its activated output z (the largest tensor of
+ * the net: N x H x W x 32) and the head's input gradient dz are therefore never stored:
+ *   xv2_bn_act_head_forward  (replaces xv2_bn_act_forward + xv2_head_conv_forward, call sites layers.py ConvLayer + unet.py
+ *     OutputBlock): logits = head(act(y * scale + shift)) in one pass over y; z stays in registers.
+ *   xv2_bn_act_head_backward (replaces xv2_head_conv_backward + xv2_bn_act_backward): both BatchNorm backward passes rebuild
+ *     dz[p][c] = sum_o dlogits[p][o] * w[o][c] per element; the second one (dy is elementwise: it walks the tensor in the head
+ *     kernel's pixel partition) also leaves the head's dw / db partials (z recomputed from y), folded in fp64 like
+ *     xv2_head_conv_backward's.  dy, dgamma, dbeta, sums2, the recorded maximum of dy, the head's dw / db and the logits are
+ *     bit-identical to the unfused calls.  workspace: xv2_bn_act_head_backward_workspace(npix, C, Cout) bytes.
+ *   xv2_conv_bn_act_head_forward = xv2_conv2d_forward_bn + xv2_bn_act_head_forward behind one call (layer-level, like
+ *     xv2_conv_bn_act_forward).
+ * Shapes: xv2_bn_act_head_supported(npix, C, Cout) - C a power of two in 4 .. 256 (C / 4 lanes per pixel), Cout 1 .. 4; dense or
+ * strided rows (ld % 4 == 0); single-process training-mode BatchNorm without a residual input.  dlogits / logits: fp32, NCHW
+ * ([N][Cout][hw]) or NHWC.  The Python layer takes this path for a head that reads one ConvLayer output with no other consumer
+ * (networks._decode); XV2_HEAD_FUSE=0 in the environment restores the unfused calls (A/B runs). */
+int xv2_bn_act_head_supported(int64_t npix, int C, int Cout);
+int xv2_bn_act_head_forward(const void* y, int ldy, const float* scale, const float* shift, int act, int64_t npix,
+                            int64_t hw, int C, int Cout, const float* w, const float* bias, float* logits,
+                            int nchw_out, int dtype, void* stream);
+size_t xv2_bn_act_head_backward_workspace(int64_t npix, int C, int Cout);
+int xv2_bn_act_head_backward(const float* dlogits, int nchw_dl, int64_t hw, const float* w, int Cout, const void* y, int ldy,
+                             const float* mean, const float* invstd, const float* gamma, const float* scale,
+                             const float* shift, int act, double count, void* dy, int lddy, int64_t npix, int C,
+                             double* sums2, float* dgamma, float* dbeta, float* dw, float* dbias, float* workspace,
+                             int dtype, void* stream);
+int xv2_conv_bn_act_head_forward(const xv2_conv_desc* d, const void* x0, int ldx0, const void* x1, int ldx1,
+                                 const void* w_ohwi, void* y, int ldy, float* stats_partials,
+                                 float* workspace, double* sums, double* scratch, double count, const float* gamma,
+                                 const float* beta, float eps, float momentum, float* running_mean, float* running_var,
+                                 float* mean, float* invstd, float* scale, float* shift, int act, int head_cout,
+                                 const float* head_w, const float* head_bias, float* logits, int nchw_out, int dtype,
+                                 void* stream);
 int xv2_bn_act_backward(const void* dz, int lddz, const void* z, int ldz, const uint8_t* zmask, const void* y,
                         int ldy, const float* mean, const float* invstd, const float* gamma,
                         const float* scale, const float* shift, int act, double count, void* dy, int lddy,

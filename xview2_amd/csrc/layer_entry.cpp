@@ -30,6 +30,24 @@ extern "C" int xv2_conv_bn_act_forward(const xv2_conv_desc* d, const void* x0, i
     return xv2_bn_act_forward(y, ldy, scale, shift, residual, ldr, act, z, ldz, npix, d->Cout, dtype, stream);
 }
 
+// The last decoder layer and the head behind it (model/layers.py:89-100 ConvLayer, then model/layers.py:171-189 OutputBlock's 1x1
+// convolution; replaces xv2_conv_bn_act_forward + xv2_head_conv_forward): convolution with statistics partials, statistics
+// reduction + coefficients, then ONE pass that applies BatchNorm + activation and the head and writes only the logits.
+extern "C" int xv2_conv_bn_act_head_forward(const xv2_conv_desc* d, const void* x0, int ldx0, const void* x1, int ldx1,
+                                            const void* w_ohwi, void* y, int ldy, float* stats_partials,
+                                            float* workspace, double* sums, double* scratch, double count, const float* gamma,
+                                            const float* beta, float eps, float momentum, float* running_mean, float* running_var,
+                                            float* mean, float* invstd, float* scale, float* shift, int act, int head_cout,
+                                            const float* head_w, const float* head_bias, float* logits, int nchw_out, int dtype,
+                                            void* stream) {
+    xv2::AmaxGuard amax_guard;      // (the convolution reads the context's sources; nothing is recorded - z is never stored)
+    int rc = xv2_conv2d_forward_bn(d, x0, ldx0, x1, ldx1, w_ohwi, y, ldy, stats_partials, workspace, 1, d->Cout, sums, scratch, count,
+                                   gamma, beta, eps, momentum, running_mean, running_var, mean, invstd, scale, shift, stream);
+    if (rc) return rc;
+    return xv2_bn_act_head_forward(y, ldy, scale, shift, act, (int64_t)d->N * d->OH * d->OW, (int64_t)d->OH * d->OW, d->Cout,
+                                   head_cout, head_w, head_bias, logits, nchw_out, dtype, stream);
+}
+
 extern "C" int xv2_bn_act_backward(const void* dz, int lddz, const void* z, int ldz, const uint8_t* zmask, const void* y,
                                    int ldy, const float* mean, const float* invstd, const float* gamma,
                                    const float* scale, const float* shift, int act, double count, void* dy, int lddy,

@@ -6,6 +6,7 @@
 // unbiased for running_var, momentum 0.1, eps 1e-5).
 #include "bn_fold.h"
 #include "amax_ctx.h"
+#include "head_fuse.h"
 #include <type_traits>
 #include <mutex>
 #include <cstring>
@@ -58,9 +59,22 @@ static ChunkGeom chunk_geom(int64_t npix, int C, int W = 4) {
     return g;
 }
 
-// MODE 0: tensor stats (x, x*x).  MODE 1: BN backward (g, g*xhat).
-template <int MODE, typename T>
+// the head behind the last decoder layer (head_fuse.h), as the BatchNorm backward passes see it: dz is never stored, a lane
+// rebuilds its 4 channels of it from the pixel's <= 4 logit gradients
+struct HeadGrad {
+    const float* dl;     // d loss / d logits, [N][Cout][hw] (nchw) or [npix][Cout]
+    const float* w;      // head weights [Cout][C]
+    int64_t hw;
+    int nchw, hw_div;    // hw_div: head_index_fast
+};
+
+// MODE 0: tensor stats (x, x*x).  MODE 1: BN backward (g, g*xhat).  MODE 2: MODE 1 with dz = head_dx4(dlogits, w) computed per
+// element, the activation mask recomputed from y (COUT = the head's
+// output channels; vector path only).
+template <int MODE, typename T, int COUT = 0>
 struct ColOp {
+    struct NoHead {};
+    typename std::conditional<MODE == 2, HeadGrad, NoHead>::type head;   // MODE2 only: no kernel argument bytes elsewhere
     const T* a;   // MODE0: x          MODE1: dz
     const T* z;   // MODE1
     const T* y;   // MODE1
@@ -72,6 +86,8 @@ struct ColOp {
     int zbits;   // z is not the activated output but a byte per float4 of it: bit k = (z[4*j + k] > 0)
     int c4tot;   // float4 per row (mask indexing)
     __device__ __forceinline__ void apply(int64_t row, int c, float& f0, float& f1) const {
+        static_assert(MODE != 2 || COUT > 0, "mode 2 needs the head's channel count");
+        static_assert(MODE != 2, "mode 2 has no generic form: vector path only (xv2_bn_act_head_supported), rows through applyh");
         if constexpr (MODE == 0) {
             // shifted sums (shift = the tensor's first row): avoids the E[x^2]-E[x]^2 cancellation when
             // |mean| >> std (e.g. split-attention bn1 over a handful of near-equal GAP values)
@@ -93,6 +109,7 @@ struct ColOp {
                                            const float4 (&mu)[Vec16<T>::NV], const float4 (&is)[Vec16<T>::NV],
                                            const float4 (&sc)[Vec16<T>::NV], const float4 (&sf)[Vec16<T>::NV]) const {
         constexpr int NV = Vec16<T>::NV;
+        static_assert(MODE != 2, "mode 2 rows go through applyh");
         if constexpr (MODE == 0) {
             float4 v[NV];
             Vec16<T>::ld(a + row * lda + c, v);
@@ -135,6 +152,25 @@ struct ColOp {
             }
         }
     }
+    // MODE 2: one row of this lane's 4 channels.  dz takes the values the unfused path stores and reads back (rounded to T);
+    // the (g, g * xhat) expressions are those of MODE 1 with z == nullptr.
+    __device__ __forceinline__ void applyh(int64_t row, int c, float4& f0, float4& f1, const float4& mu, const float4& is,
+                                           const float4& sc, const float4& sf, const float4 (&ww)[COUT > 0 ? COUT : 1]) const {
+        if constexpr (MODE == 2) {
+            float g[COUT];
+            head_load_g<COUT>(head.dl, head_index_fast(head.nchw, row, head.hw, COUT, head.hw_div), g);
+            const float4 yy = ld4(y + row * ldy + c);
+            const float4 d = as_loaded(stored4<T>(head_dx4<COUT>(g, ww)));
+            // (MODE 1's sums as the compiler contracts them - the product of f0's term unrounded inside an fma, f1's g rounded first -
+            //  spelled out, so that this instantiation cannot contract them any other way: dgamma / dbeta stay bit-equal)
+            const float ax = act_grad_from_pre(__fmaf_rn(yy.x, sc.x, sf.x), act), ay = act_grad_from_pre(__fmaf_rn(yy.y, sc.y, sf.y), act);
+            const float az = act_grad_from_pre(__fmaf_rn(yy.z, sc.z, sf.z), act), aw = act_grad_from_pre(__fmaf_rn(yy.w, sc.w, sf.w), act);
+            const float4 gg = as_loaded(make_float4(d.x * ax, d.y * ay, d.z * az, d.w * aw));
+            f0.x = __fmaf_rn(d.x, ax, f0.x); f0.y = __fmaf_rn(d.y, ay, f0.y); f0.z = __fmaf_rn(d.z, az, f0.z); f0.w = __fmaf_rn(d.w, aw, f0.w);
+            const float4 xh = as_loaded(make_float4((yy.x - mu.x) * is.x, (yy.y - mu.y) * is.y, (yy.z - mu.z) * is.z, (yy.w - mu.w) * is.w));
+            f1.x = __fmaf_rn(gg.x, xh.x, f1.x); f1.y = __fmaf_rn(gg.y, xh.y, f1.y); f1.z = __fmaf_rn(gg.z, xh.z, f1.z); f1.w = __fmaf_rn(gg.w, xh.w, f1.w);
+        }
+    }
 };
 
 // XV2_BN_REVERSE (A/B runs): bit 0 = the backward apply, bit 1 = the forward apply, bit 2 = the backward column sums walk
@@ -146,8 +182,8 @@ static int bn_reverse(int bit) {
     return (v >> bit) & 1;
 }
 
-template <int MODE, typename T>
-__global__ void __launch_bounds__(256) column_partials_kernel(ColOp<MODE, T> op, int64_t npix, int C, int rpb, int cgw,
+template <int MODE, typename T, int COUT = 0>
+__global__ void __launch_bounds__(256) column_partials_kernel(ColOp<MODE, T, COUT> op, int64_t npix, int C, int rpb, int cgw,
                                                               double* __restrict__ part, int rev) {
     __shared__ float sh[256 * 8 * Vec16<T>::NV];
     const int tid = threadIdx.x;
@@ -167,10 +203,10 @@ __global__ void __launch_bounds__(256) column_partials_kernel(ColOp<MODE, T> op,
 #pragma unroll
         for (int q = 0; q < NV; ++q) {
             f0[q] = f1[q] = g0[q] = g1[q] = mu[q] = is[q] = sc[q] = sf[q] = make_float4(0, 0, 0, 0);
-            if constexpr (MODE == 1) {
+            if constexpr (MODE >= 1) {
                 mu[q] = *reinterpret_cast<const float4*>(op.mean + cb + 4 * q);
                 is[q] = *reinterpret_cast<const float4*>(op.invstd + cb + 4 * q);
-                if (!op.z) {
+                if (MODE == 2 || !op.z) {
                     sc[q] = *reinterpret_cast<const float4*>(op.scale + cb + 4 * q);
                     sf[q] = *reinterpret_cast<const float4*>(op.shift + cb + 4 * q);
                 }
@@ -180,11 +216,23 @@ __global__ void __launch_bounds__(256) column_partials_kernel(ColOp<MODE, T> op,
         }
         // two rows in flight per iteration (independent accumulators): more bytes outstanding per lane
         int64_t r = r0 + ty;
-        for (; r + rpp < r1; r += 2 * rpp) {
-            op.applyv(r, cb, f0, f1, mu, is, sc, sf);
-            op.applyv(r + rpp, cb, g0, g1, mu, is, sc, sf);
+        constexpr int HC = COUT > 0 ? COUT : 1;
+        float4 hww[HC];      // MODE 2: the head's weights of this lane's channels
+        if constexpr (MODE == 2) {
+            static_assert(NV == 1, "the head owns 4 channels per lane");
+            head_load_w<COUT>(op.head.w, C, cb, hww);
+            for (; r + rpp < r1; r += 2 * rpp) {
+                op.applyh(r, cb, f0[0], f1[0], mu[0], is[0], sc[0], sf[0], hww);
+                op.applyh(r + rpp, cb, g0[0], g1[0], mu[0], is[0], sc[0], sf[0], hww);
+            }
+            if (r < r1) op.applyh(r, cb, f0[0], f1[0], mu[0], is[0], sc[0], sf[0], hww);
+        } else {
+            for (; r + rpp < r1; r += 2 * rpp) {
+                op.applyv(r, cb, f0, f1, mu, is, sc, sf);
+                op.applyv(r + rpp, cb, g0, g1, mu, is, sc, sf);
+            }
+            if (r < r1) op.applyv(r, cb, f0, f1, mu, is, sc, sf);
         }
-        if (r < r1) op.applyv(r, cb, f0, f1, mu, is, sc, sf);
         // per 4-channel group q: the fold below is the one the 4-wide layout performs (same order, same result)
 #pragma unroll
         for (int q = 0; q < NV; ++q) {
@@ -213,7 +261,7 @@ __global__ void __launch_bounds__(256) column_partials_kernel(ColOp<MODE, T> op,
                 o[1] = a1[k];
             }
         }
-    } else {
+    } else if constexpr (MODE != 2) {
         // generic fallback: 64 channel lanes x 4 row lanes
         const int tx = tid & 63, ty = tid >> 6;
         for (int cb = 0; cb < C; cb += 64) {
@@ -522,13 +570,7 @@ __global__ void __launch_bounds__(256) bn_act_fwd_kernel(const T* __restrict__ y
             for (int q = 0; q < NV; ++q) {
                 const float4 sc = *reinterpret_cast<const float4*>(scale + c + 4 * q);
                 const float4 sh = *reinterpret_cast<const float4*>(shift + c + 4 * q);
-                o[q].x = __fmaf_rn(v[q].x, sc.x, sh.x); o[q].y = __fmaf_rn(v[q].y, sc.y, sh.y);
-                o[q].z = __fmaf_rn(v[q].z, sc.z, sh.z); o[q].w = __fmaf_rn(v[q].w, sc.w, sh.w);
-                if (res) {
-                    o[q].x += r[q].x; o[q].y += r[q].y; o[q].z += r[q].z; o[q].w += r[q].w;
-                }
-                o[q].x = apply_act(o[q].x, act); o[q].y = apply_act(o[q].y, act);
-                o[q].z = apply_act(o[q].z, act); o[q].w = apply_act(o[q].w, act);
+                o[q] = bn_act_apply4(v[q], sc, sh, res ? &r[q] : nullptr, act);
                 mbits |= (unsigned)((o[q].x > 0.f) | ((o[q].y > 0.f) << 1) | ((o[q].z > 0.f) << 2) | ((o[q].w > 0.f) << 3)) << (8 * q);
                 zmax = amax_acc(zmax, o[q]);
             }
@@ -551,6 +593,47 @@ __global__ void __launch_bounds__(256) bn_act_fwd_kernel(const T* __restrict__ y
         }
     }
     if (amax) amax_record(amax, zmax, amax_red);
+}
+
+// BatchNorm apply + activation + the <= 4-channel head of the last decoder layer in ONE pass (model/layers.py:93-94 ConvLayer's norm
+// and activation, then OutputBlock's 1x1 convolution, model/layers.py:177,180): z = act(y * scale + shift) lives in registers only -
+// the head is its single consumer and the BatchNorm backward recomputes the activation mask from y - and only the logits are
+// written.  head_fwd_kernel's lane <-> channel ownership (4 channels per lane, L = C / 4 lanes per pixel, the same shuffle tree)
+// and the shared per-lane functions of head_fuse.h: the logits are bit-identical to bn_act_fwd_kernel + head_fwd_kernel.  C = 4 * L,
+// so a lane keeps its coefficients and head weights in registers.  Pixels are walked last-to-first like bn_act_fwd_kernel (rev):
+// the convolution that wrote y finished with its last rows.  No amax record: no MFMA kernel reads z.
+template <int COUT, typename T>
+__global__ void __launch_bounds__(256) bn_act_head_fwd_kernel(const T* __restrict__ y, int ldy, const float* __restrict__ scale,
+                                                               const float* __restrict__ shift, int act, int64_t npix, int64_t hw,
+                                                               int C, const float* __restrict__ w, const float* __restrict__ bias,
+                                                               float* __restrict__ logits, int nchw, int hw_div, int L, int rev) {
+    const int lane_in = threadIdx.x % L;
+    const int gpb = 256 / L;
+    const int c = lane_in * 4;
+    const float4 sc = *reinterpret_cast<const float4*>(scale + c), sh = *reinterpret_cast<const float4*>(shift + c);
+    float4 ww[COUT];
+    head_load_w<COUT>(w, C, c, ww);
+    const int64_t gstride = (int64_t)gridDim.x * gpb;
+    auto pixel = [&](int64_t p, const float4& v) {
+        float acc[COUT];
+#pragma unroll
+        for (int o = 0; o < COUT; ++o) acc[o] = 0.f;
+        head_dot4<COUT>(as_loaded(stored4<T>(bn_act_apply4(v, sc, sh, nullptr, act))), ww, acc);
+        head_lane_sum<COUT>(acc, L);
+        if (lane_in == 0) head_store<COUT>(logits, acc, bias, head_index_fast(nchw, p, hw, COUT, hw_div));
+    };
+    // two pixels in flight per lane: the loads are all this pass waits for
+    int64_t j = (int64_t)blockIdx.x * gpb + threadIdx.x / L;
+    for (; j + gstride < npix; j += 2 * gstride) {
+        const int64_t p0 = rev ? npix - 1 - j : j, p1 = rev ? npix - 1 - (j + gstride) : j + gstride;
+        const float4 v0 = ld4(y + p0 * ldy + c), v1 = ld4(y + p1 * ldy + c);
+        pixel(p0, v0);
+        pixel(p1, v1);
+    }
+    if (j < npix) {
+        const int64_t p0 = rev ? npix - 1 - j : j;
+        pixel(p0, ld4(y + p0 * ldy + c));
+    }
 }
 
 template <bool VEC, typename T>
@@ -697,6 +780,94 @@ __global__ void __launch_bounds__(256) bn_act_bwd_rows_kernel(const T* __restric
         unsigned m0;
         fetch(r, d0, z0, y0, m0);
         row(r, d0, z0, y0, m0);
+    }
+    if (amax) amax_record(amax, dmax, amax_red);
+}
+
+// The head form of the apply pass (training mode, no residual; C = 4 * L): dz is not read but rebuilt per element from the pixel's
+// logit gradients (head_dx4, rounded to the storage type like the tensor head_bwd_kernel would have stored), dy is the expression
+// of bn_act_bwd_rows_kernel, and - dy being elementwise, the pass is free to walk the tensor as it likes - the walk is
+// head_bwd_kernel's: block b, group grp takes pixels b * gpb + grp, + gridDim * gpb, ...; the head's dw / db partials (z recomputed
+// from the y this pass reads anyway) are therefore head_bwd_kernel's sums in head_bwd_kernel's order, folded over the block's
+// groups in the same order: dw / db come out bit-identical to the unfused path.  part: [gridDim][COUT][C + 1].
+template <int COUT, typename T>
+__global__ void __launch_bounds__(256) bn_act_bwd_rows_head_kernel(const HeadGrad head, const T* __restrict__ y, int ldy,
+                                                                    const float* __restrict__ mean, const float* __restrict__ invstd,
+                                                                    const float* __restrict__ gamma, const float* __restrict__ scale,
+                                                                    const float* __restrict__ shift, const double* __restrict__ sums2,
+                                                                    double count, int act, T* __restrict__ dy, int lddy, int64_t npix,
+                                                                    int C, int L, float* __restrict__ part, unsigned* __restrict__ amax) {
+    __shared__ float sh[256 * 4 * COUT];      // [gpb][COUT][4 * L]
+    __shared__ float amax_red[4];
+    float dmax = 0.f;       // F16X2: max |dy| of this block
+    const int tid = threadIdx.x;
+    const int lane_in = tid % L, grp = tid / L, gpb = 256 / L;
+    const int c = lane_in * 4;
+    const float inv_count = (float)(1.0 / count);
+    const float4 mu = *reinterpret_cast<const float4*>(mean + c), is = *reinterpret_cast<const float4*>(invstd + c);
+    const float4 sc = *reinterpret_cast<const float4*>(scale + c), sf = *reinterpret_cast<const float4*>(shift + c);
+    float gi[4], sg[4], sgx[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        gi[k] = (gamma ? gamma[c + k] : 1.f) * invstd[c + k];
+        sg[k] = (float)sums2[(c + k) * 2] * inv_count;
+        sgx[k] = (float)sums2[(c + k) * 2 + 1] * inv_count;
+    }
+    float4 ww[COUT], dwacc[COUT];
+    float dbacc[COUT];
+    head_load_w<COUT>(head.w, C, c, ww);
+#pragma unroll
+    for (int o = 0; o < COUT; ++o) {
+        dwacc[o] = make_float4(0, 0, 0, 0);
+        dbacc[o] = 0.f;
+    }
+    const int64_t gstride = (int64_t)gridDim.x * gpb;
+    for (int64_t p = (int64_t)blockIdx.x * gpb + grp; p < npix; p += gstride) {
+        float g[COUT];
+        head_load_g<COUT>(head.dl, head_index_fast(head.nchw, p, head.hw, COUT, head.hw_div), g);
+        const float4 yy = ld4(y + p * ldy + c);
+        const float4 d = as_loaded(stored4<T>(head_dx4<COUT>(g, ww)));
+        const float4 pre = make_float4(__fmaf_rn(yy.x, sc.x, sf.x), __fmaf_rn(yy.y, sc.y, sf.y), __fmaf_rn(yy.z, sc.z, sf.z),
+                                       __fmaf_rn(yy.w, sc.w, sf.w));
+        // dy = gi * (g - sg - xhat * sgx), spelled as bn_act_bwd_rows_kernel compiles it: g and xhat rounded, then one fma
+        const float4 gg = as_loaded(make_float4(d.x * act_grad_from_pre(pre.x, act), d.y * act_grad_from_pre(pre.y, act),
+                                                d.z * act_grad_from_pre(pre.z, act), d.w * act_grad_from_pre(pre.w, act)));
+        const float4 xh = as_loaded(make_float4((yy.x - mu.x) * is.x, (yy.y - mu.y) * is.y, (yy.z - mu.z) * is.z, (yy.w - mu.w) * is.w));
+        float4 o;
+        o.x = gi[0] * __fmaf_rn(-xh.x, sgx[0], gg.x - sg[0]); o.y = gi[1] * __fmaf_rn(-xh.y, sgx[1], gg.y - sg[1]);
+        o.z = gi[2] * __fmaf_rn(-xh.z, sgx[2], gg.z - sg[2]); o.w = gi[3] * __fmaf_rn(-xh.w, sgx[3], gg.w - sg[3]);
+        dmax = amax_acc(dmax, o);
+        st4(dy + p * lddy + c, o);
+        // the head's own gradients, as head_bwd_kernel takes them from the stored z
+        const float4 z = as_loaded(stored4<T>(make_float4(apply_act(pre.x, act), apply_act(pre.y, act), apply_act(pre.z, act),
+                                                           apply_act(pre.w, act))));
+        head_dw4<COUT>(g, z, dwacc);
+        if (lane_in == 0) {
+#pragma unroll
+            for (int o2 = 0; o2 < COUT; ++o2) dbacc[o2] += g[o2];
+        }
+    }
+    // fold over the groups of this block: head_bwd_kernel's, in its order
+    float* mypart = part + (size_t)blockIdx.x * COUT * (C + 1);
+#pragma unroll
+    for (int o = 0; o < COUT; ++o) *reinterpret_cast<float4*>(sh + ((grp * COUT + o) * L + lane_in) * 4) = dwacc[o];
+    __syncthreads();
+    for (int i = tid; i < COUT * L * 4; i += 256) {
+        const int o = i / (L * 4), k = i % (L * 4);
+        float s = 0.f;
+        for (int q = 0; q < gpb; ++q) s += sh[((q * COUT + o) * L) * 4 + k];
+        mypart[o * (C + 1) + k] = s;
+    }
+    __syncthreads();
+    if (lane_in == 0) {
+#pragma unroll
+        for (int o = 0; o < COUT; ++o) sh[grp * COUT + o] = dbacc[o];
+    }
+    __syncthreads();
+    if (tid < COUT) {
+        float s = 0.f;
+        for (int q = 0; q < gpb; ++q) s += sh[q * COUT + tid];
+        mypart[tid * (C + 1) + C] = s;
     }
     if (amax) amax_record(amax, dmax, amax_red);
 }
@@ -1102,6 +1273,121 @@ extern "C" int xv2_bn_act_backward_apply_mask(const void* dz, int lddz, const ui
                                                          (const T*)y, ldy, mean, invstd, gamma, nullptr, nullptr, sums2,
                                                          count, act, train, (T*)dy, lddy, (T*)dres, lddres, npix, C,
                                                          stream));
+}
+
+// ---- the head of the last decoder layer inside the BatchNorm passes (include/xv2.h "head fusion") ----
+extern "C" int xv2_bn_act_head_supported(int64_t npix, int C, int Cout) {
+    if (npix <= 0 || C < 4 || C > 256 || (C & (C - 1)) || Cout < 1 || Cout > HEAD_MAX_COUT) return 0;
+    // C / 4 lanes per pixel = the head's L = the BatchNorm kernels' lanes per row, one 4-channel group per lane, one channel group
+    const ChunkGeom g = chunk_geom(npix, C, 4);
+    return (head_lanes(C) * 4 == C && g.cgw == C && g.groups == 1) ? 1 : 0;
+}
+
+template <typename T>
+static int bn_act_head_forward_impl(const T* y, int ldy, const float* scale, const float* shift, int act, int64_t npix, int64_t hw,
+                                    int C, int Cout, const float* w, const float* bias, float* logits, int nchw_out, void* stream) {
+    XV2_CHECK_ARG(y && scale && shift && w && logits && hw > 0, "bn_act_head_forward: null argument");
+    XV2_CHECK_ARG(xv2_bn_act_head_supported(npix, C, Cout), "bn_act_head_forward: no fused form for C=%d Cout=%d", C, Cout);
+    XV2_CHECK_ARG(vec_ok(C, sizeof(T), {ldy}, {y}, 4) && vec_ok(C, 4, {}, {scale, shift, w}), "bn_act_head_forward: unaligned operand");
+    const int L = C / 4;
+    // (a pixel group per thread group, two pixels in flight per lane: the grid of bn_act_fwd_kernel over half the elements)
+    const int grid = ew_grid(cdiv(npix * L, 2));
+    hipStream_t st = (hipStream_t)stream;
+    prof_begin(head_prof_id(2), 0.0, 0.0, st);
+#define LAUNCH_BHF(CO)                                                                                                     \
+    hipLaunchKernelGGL((bn_act_head_fwd_kernel<CO, T>), dim3(grid), dim3(256), 0, st, y, ldy, scale, shift, act, npix, hw, C, w, \
+                       bias, logits, nchw_out, head_hw_div(npix, hw), L, bn_reverse(1))
+    switch (Cout) {
+        case 1: LAUNCH_BHF(1); break;
+        case 2: LAUNCH_BHF(2); break;
+        case 3: LAUNCH_BHF(3); break;
+        default: LAUNCH_BHF(4); break;
+    }
+#undef LAUNCH_BHF
+    prof_end(st);
+    XV2_CHECK_LAUNCH();
+    return XV2_OK;
+}
+
+extern "C" int xv2_bn_act_head_forward(const void* y, int ldy, const float* scale, const float* shift, int act, int64_t npix,
+                                       int64_t hw, int C, int Cout, const float* w, const float* bias, float* logits,
+                                       int nchw_out, int dtype, void* stream) {
+    XV2_CHECK_DTYPE(dtype);
+    AmaxGuard amax_guard;      // (nothing is recorded: z is never stored)
+    XV2_DISPATCH_DTYPE(dtype, return bn_act_head_forward_impl<T>((const T*)y, ldy, scale, shift, act, npix, hw, C, Cout, w, bias,
+                                                                logits, nchw_out, stream));
+}
+
+static size_t bn_head_part_offset(int64_t npix, int C) {
+    return (xv2_bn_backward_workspace(npix, C) + 15) & ~(size_t)15;
+}
+extern "C" size_t xv2_bn_act_head_backward_workspace(int64_t npix, int C, int Cout) {
+    return bn_head_part_offset(npix, C) + (size_t)HEAD_BLOCKS * Cout * (C + 1) * sizeof(float);
+}
+
+template <typename T, int COUT>
+static int bn_act_head_backward_impl(const float* dlogits, int nchw, int64_t hw, const float* w, const T* y, int ldy, const float* mean,
+                                     const float* invstd, const float* gamma, const float* scale, const float* shift, int act,
+                                     double count, T* dy, int lddy, int64_t npix, int C, double* sums2, float* dgamma, float* dbeta,
+                                     float* dw, float* dbias, float* workspace, hipStream_t st) {
+    unsigned* amax = std::is_same<T, float>::value ? amax_ctx().out : nullptr;      // F16X2: record max |dy| (fp32 tensors)
+    const ChunkGeom g = chunk_geom(npix, C, 4);
+    HeadGrad hg;
+    hg.dl = dlogits; hg.w = w; hg.hw = hw; hg.nchw = nchw; hg.hw_div = head_hw_div(npix, hw);
+    float* hpart = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + bn_head_part_offset(npix, C));
+    ColOp<2, T, COUT> op;
+    op.head = hg;
+    op.a = nullptr; op.lda = 0; op.z = nullptr; op.ldz = 0; op.y = y; op.ldy = ldy; op.mean = mean; op.invstd = invstd;
+    op.scale = scale; op.shift = shift; op.act = act; op.zbits = 0; op.c4tot = C / 4;
+    size_t part = (size_t)g.chunks * C * 2 * sizeof(double);
+    part = (part + 15) & ~(size_t)15;
+    double* dpart = reinterpret_cast<double*>(workspace);
+    double* scratch = reinterpret_cast<double*>(reinterpret_cast<char*>(workspace) + part);
+    // pass 1: (sum g, sum g * xhat) per channel, in the unfused pass's row chunks; then its fold
+    prof_begin(head_prof_id(3), 0.0, 0.0, st);
+    hipLaunchKernelGGL((column_partials_kernel<2, T, COUT>), dim3((unsigned)g.chunks, 1), dim3(256), 0, st, op, npix, C, g.rpb, g.cgw,
+                       dpart, bn_reverse(2));
+    prof_end(st);
+    XV2_CHECK_LAUNCH();
+    int rc = reduce_stats<double>(dpart, g.chunks, C, sums2, scratch, st, dbeta, dgamma);
+    if (rc) return rc;
+    // pass 2: dy and the head's dw / db partials in head_bwd_kernel's geometry; then head_bwd_kernel's fold
+    const int L = C / 4;
+    const int grid = (int)std::min<int64_t>(cdiv(npix, 256 / L), HEAD_BLOCKS);
+    prof_begin(head_prof_id(4), 0.0, 0.0, st);
+    hipLaunchKernelGGL((bn_act_bwd_rows_head_kernel<COUT, T>), dim3(grid), dim3(256), 0, st, hg, y, ldy, mean, invstd, gamma, scale,
+                       shift, sums2, count, act, dy, lddy, npix, C, L, hpart, amax);
+    prof_end(st);
+    XV2_CHECK_LAUNCH();
+    return head_bwd_reduce_launch(hpart, grid, COUT, C, dw, dbias, st);
+}
+
+extern "C" int xv2_bn_act_head_backward(const float* dlogits, int nchw_dl, int64_t hw, const float* w, int Cout, const void* y, int ldy,
+                                        const float* mean, const float* invstd, const float* gamma, const float* scale,
+                                        const float* shift, int act, double count, void* dy, int lddy, int64_t npix, int C,
+                                        double* sums2, float* dgamma, float* dbeta, float* dw, float* dbias, float* workspace,
+                                        int dtype, void* stream) {
+    XV2_CHECK_DTYPE(dtype);
+    AmaxGuard amax_guard;
+    XV2_CHECK_ARG(dlogits && w && y && mean && invstd && scale && shift && dy && sums2 && dw && workspace && hw > 0,
+                  "bn_act_head_backward: null argument");
+    XV2_CHECK_ARG(xv2_bn_act_head_supported(npix, C, Cout), "bn_act_head_backward: no fused form for C=%d Cout=%d", C, Cout);
+    const size_t es = dtype == XV2_BF16 ? 2 : 4;
+    XV2_CHECK_ARG(vec_ok(C, es, {ldy, lddy}, {y, dy}, 4) && vec_ok(C, 4, {}, {w, mean, invstd, scale, shift, gamma}),
+                  "bn_act_head_backward: unaligned operand");
+    hipStream_t st = (hipStream_t)stream;
+#define BHB(CO)                                                                                                                   \
+    XV2_DISPATCH_DTYPE(dtype, return (bn_act_head_backward_impl<T, CO>(dlogits, nchw_dl, hw, w, (const T*)y, ldy, mean, invstd, gamma, \
+                                                                      scale, shift, act, count, (T*)dy, lddy, npix, C, sums2, dgamma, \
+                                                                      dbeta, dw, dbias, workspace, st)))
+    switch (Cout) {
+        case 1: BHB(1);
+        case 2: BHB(2);
+        case 3: BHB(3);
+        default: BHB(4);
+    }
+#undef BHB
+    return XV2_OK;      // (not reached: every case returns)
 }
 
 extern "C" int xv2_bn_rows_forward(const float* y, int rows, int C, int parts, const float* gamma, const float* beta, float eps,

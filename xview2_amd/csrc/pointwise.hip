@@ -7,6 +7,7 @@
 // All reductions are two-level with a fixed order (deterministic), no atomics.
 #include "xv2_common.h"
 #include "amax_ctx.h"
+#include "head_fuse.h"
 #include "../../include/xv2.h"
 #include <algorithm>
 #include <stdlib.h>
@@ -23,7 +24,6 @@ static inline int grid_for(int64_t total, int cap = 8192) {
 // ----------------------------------------------------------------------------------- head conv
 // L lanes cooperate on one pixel (L = min(64, Cin/4), power of two); each lane owns 4 channels
 // of every 4*L chunk.  COUT <= 4.
-constexpr int HEAD_BLOCKS = 1024;
 
 template <int COUT, typename T>
 __global__ void __launch_bounds__(256) head_fwd_kernel(const T* __restrict__ x, int ldx, int64_t npix,
@@ -41,27 +41,12 @@ __global__ void __launch_bounds__(256) head_fwd_kernel(const T* __restrict__ x, 
         for (int o = 0; o < COUT; ++o) acc[o] = 0.f;
         for (int c = lane_in * 4; c < Cin; c += 4 * L) {
             const float4 v = ld4(x + p * ldx + c);
-#pragma unroll
-            for (int o = 0; o < COUT; ++o) {
-                const float4 ww = *reinterpret_cast<const float4*>(w + o * Cin + c);
-                acc[o] += v.x * ww.x + v.y * ww.y + v.z * ww.z + v.w * ww.w;
-            }
+            float4 ww[COUT];
+            head_load_w<COUT>(w, Cin, c, ww);
+            head_dot4<COUT>(v, ww, acc);
         }
-#pragma unroll
-        for (int o = 0; o < COUT; ++o)
-            for (int s = L >> 1; s > 0; s >>= 1) acc[o] += __shfl_xor(acc[o], s, 64);
-        if (lane_in == 0) {
-#pragma unroll
-            for (int o = 0; o < COUT; ++o) {
-                const float r = acc[o] + (bias ? bias[o] : 0.f);
-                if (nchw) {
-                    const int64_t n = p / hw, q = p - n * hw;
-                    y[(n * COUT + o) * hw + q] = r;
-                } else {
-                    y[p * COUT + o] = r;
-                }
-            }
-        }
+        head_lane_sum<COUT>(acc, L);
+        if (lane_in == 0) head_store<COUT>(y, acc, bias, head_index(nchw, p, hw, COUT));
     }
 }
 
@@ -87,29 +72,18 @@ __global__ void __launch_bounds__(256) head_bwd_kernel(const T* __restrict__ x, 
         const int c = cb + lane_in * 4;
         float4 ww[COUT];
         float4 dwacc[COUT];
+        head_load_w<COUT>(w, Cin, c, ww);
 #pragma unroll
-        for (int o = 0; o < COUT; ++o) {
-            ww[o] = *reinterpret_cast<const float4*>(w + o * Cin + c);
-            dwacc[o] = make_float4(0, 0, 0, 0);
-        }
+        for (int o = 0; o < COUT; ++o) dwacc[o] = make_float4(0, 0, 0, 0);
         for (int64_t p = g0; p < npix; p += gstride) {
             float g[COUT];
-#pragma unroll
-            for (int o = 0; o < COUT; ++o) {
-                if (nchw) {
-                    const int64_t n = p / hw, q = p - n * hw;
-                    g[o] = dy[(n * COUT + o) * hw + q];
-                } else {
-                    g[o] = dy[p * COUT + o];
-                }
-            }
+            head_load_g<COUT>(dy, head_index(nchw, p, hw, COUT), g);
             const float4 v = ld4(x + p * ldx + c);
-            float4 d = make_float4(0, 0, 0, 0);
+            const float4 d = head_dx4<COUT>(g, ww);
+            head_dw4<COUT>(g, v, dwacc);
+            if (cb == 0 && lane_in == 0) {
 #pragma unroll
-            for (int o = 0; o < COUT; ++o) {
-                d.x += g[o] * ww[o].x; d.y += g[o] * ww[o].y; d.z += g[o] * ww[o].z; d.w += g[o] * ww[o].w;
-                dwacc[o].x += g[o] * v.x; dwacc[o].y += g[o] * v.y; dwacc[o].z += g[o] * v.z; dwacc[o].w += g[o] * v.w;
-                if (cb == 0 && lane_in == 0) dbacc[o] += g[o];
+                for (int o = 0; o < COUT; ++o) dbacc[o] += g[o];
             }
             if (dx) st4(dx + p * lddx + c, d);
         }
@@ -592,10 +566,17 @@ __global__ void rsoftmax_bwd_kernel(const float* __restrict__ a, const float* __
     dl[n * 2 * C + C + c] = a1 * (d1 - dot);
 }
 
-static int pick_L(int Cin) {
-    int L = 1;
-    while (L * 2 <= 64 && L * 2 * 4 <= Cin) L *= 2;
-    return L;
+int head_prof_id(int which) {
+    static const int ids[5] = {prof_register("head_fwd_kernel"), prof_register("head_bwd_kernel"), prof_register("bn_act_head_fwd_kernel"),
+                               prof_register("column_partials_kernel<head>"), prof_register("bn_act_bwd_rows_head_kernel")};
+    return ids[which];
+}
+
+int head_bwd_reduce_launch(const float* part, int nblocks, int Cout, int Cin, float* dw, float* db, hipStream_t stream) {
+    hipLaunchKernelGGL(head_bwd_reduce_kernel, dim3((unsigned)cdiv((int64_t)Cout * (Cin + 1) * 64, 256)), dim3(256), 0, stream,
+                       part, nblocks, Cout, Cin, dw, db);
+    XV2_CHECK_LAUNCH();
+    return XV2_OK;
 }
 
 }  // namespace xv2
@@ -607,10 +588,11 @@ static int head_conv_forward_impl(const T* x, int ldx, int64_t npix, int64_t hw,
                                   const float* bias, float* y, int nchw_out, void* stream) {
     XV2_CHECK_ARG(Cout >= 1 && Cout <= 4, "head_conv: Cout=%d must be in 1..4", Cout);
     XV2_CHECK_ARG(Cin % 4 == 0 && ldx % 4 == 0, "head_conv: Cin=%d must be a multiple of 4", Cin);
-    const int L = pick_L(Cin);
+    const int L = head_lanes(Cin);
     XV2_CHECK_ARG(Cin % (4 * L) == 0, "head_conv: Cin=%d unsupported", Cin);
     const int grid = (int)std::min<int64_t>(cdiv(npix, 256 / L), 16384);
     hipStream_t st = (hipStream_t)stream;
+    prof_begin(head_prof_id(0), 0.0, 0.0, st);
 #define LAUNCH_HF(CO) \
     hipLaunchKernelGGL((head_fwd_kernel<CO, T>), dim3(grid), dim3(256), 0, st, x, ldx, npix, hw, Cin, w, bias, y, nchw_out, L)
     switch (Cout) {
@@ -620,6 +602,7 @@ static int head_conv_forward_impl(const T* x, int ldx, int64_t npix, int64_t hw,
         default: LAUNCH_HF(4); break;
     }
 #undef LAUNCH_HF
+    prof_end(st);
     XV2_CHECK_LAUNCH();
     return XV2_OK;
 }
@@ -641,11 +624,12 @@ static int head_conv_backward_impl(const T* x, int ldx, const float* dy, int64_t
                                    float* workspace, void* stream) {
     XV2_CHECK_ARG(Cout >= 1 && Cout <= 4, "head_conv: Cout=%d must be in 1..4", Cout);
     XV2_CHECK_ARG(Cin % 4 == 0 && ldx % 4 == 0 && (!dx || lddx % 4 == 0), "head_conv: Cin=%d must be a multiple of 4", Cin);
-    const int L = pick_L(Cin);
+    const int L = head_lanes(Cin);
     XV2_CHECK_ARG(Cin % (4 * L) == 0, "head_conv: Cin=%d unsupported", Cin);
     int grid = (int)std::min<int64_t>(cdiv(npix, 256 / L), HEAD_BLOCKS);
     hipStream_t st = (hipStream_t)stream;
     const size_t smem = (size_t)(256 / L) * Cout * L * 4 * sizeof(float);
+    prof_begin(head_prof_id(1), 0.0, 0.0, st);
 #define LAUNCH_HB(CO)                                                                                        \
     hipLaunchKernelGGL((head_bwd_kernel<CO, T>), dim3(grid), dim3(256), smem, st, x, ldx, dy, npix, hw, Cin, w, \
                        nchw_dy, dx, lddx, workspace, L)
@@ -656,11 +640,9 @@ static int head_conv_backward_impl(const T* x, int ldx, const float* dy, int64_t
         default: LAUNCH_HB(4); break;
     }
 #undef LAUNCH_HB
+    prof_end(st);
     XV2_CHECK_LAUNCH();
-    hipLaunchKernelGGL(head_bwd_reduce_kernel, dim3((unsigned)cdiv((int64_t)Cout * (Cin + 1) * 64, 256)), dim3(256), 0, st,
-                       workspace, grid, Cout, Cin, dw, dbias);
-    XV2_CHECK_LAUNCH();
-    return XV2_OK;
+    return head_bwd_reduce_launch(workspace, grid, Cout, Cin, dw, dbias, st);
 }
 extern "C" int xv2_head_conv_backward(const void* x, int ldx, const float* dy, int64_t npix, int64_t hw, int Cin,
                                       int Cout, const float* w, int nchw_dy, void* dx, int lddx, float* dw,
@@ -710,7 +692,7 @@ extern "C" int xv2_gate_mul_backward(const void* skip, int lds, const float* gat
                                      float* dgate, int64_t npix, int C, int dtype, void* stream) {
     XV2_CHECK_ARG(C % 4 == 0 && lds % 4 == 0, "gate_mul: C must be a multiple of 4");
     XV2_CHECK_DTYPE(dtype);
-    const int L = pick_L(C);
+    const int L = head_lanes(C);
     XV2_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(gate_mul_bwd_kernel<T>,
                                                  dim3((unsigned)std::min<int64_t>(cdiv(npix, 256 / L), 16384)), dim3(256), 0,
                                                  (hipStream_t)stream, (const T*)skip, lds, gate, (const T*)dout,

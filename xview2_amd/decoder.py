@@ -20,7 +20,12 @@ class ConvLayer(nn.Module):  # layers.py:89-100
         self.conv = nn.Conv2d(in_channels, out_channels, kernel_size=3, padding=1, bias=False)
         self.batch_norm = nn.BatchNorm2d(out_channels, affine=True)
 
-    def forward(self, x0, x1=None, passthrough=0):
+    def forward(self, x0, x1=None, passthrough=0, head=None):
+        """head: the 1x1 convolution of an OutputBlock that is this layer's only consumer - the layer then returns that head's
+        NCHW logits instead of its own output (xnn.conv_bn_act_head)"""
+        if head is not None:
+            assert not passthrough
+            return xnn.conv_bn_act_head(self.conv, self.batch_norm, head, x0, x1, act=ops.ACT_LEAKY, nchw_out=True)
         return xnn.conv_bn_act(self.conv, self.batch_norm, x0, x1, act=ops.ACT_LEAKY, passthrough=passthrough)
 
 
@@ -30,8 +35,8 @@ class ConvBlock(nn.Module):  # layers.py:119-128
         self.conv1 = ConvLayer(in_channels, out_channels)
         self.conv2 = ConvLayer(out_channels, out_channels)
 
-    def forward(self, x0, x1=None):
-        return self.conv2(self.conv1(x0, x1))
+    def forward(self, x0, x1=None, head=None):
+        return self.conv2(self.conv1(x0, x1), head=head)
 
 
 class AttentionLayer(nn.Module):  # layers.py:68-77
@@ -78,7 +83,8 @@ class UpsampleBlock(nn.Module):  # layers.py:131-168
 
     alias_request, alias_out = False, None      # xnn.stage_with_input_alias: `inputs` also feeds a deep-supervision head
 
-    def forward(self, inputs, skip):
+    def forward(self, inputs, skip, head=None):
+        """head: see ConvLayer.forward - handed to the block's last layer"""
         if self.dec_interp:
             y = xnn.conv(self.conv, inputs)
             out = ops.BilinearFn.apply(y, 2 * y.shape[1], 2 * y.shape[2])
@@ -87,7 +93,7 @@ class UpsampleBlock(nn.Module):  # layers.py:131-168
         else:
             out = self.conv_tranpose(inputs)
         if self.skip_channels == 0:
-            return self.conv_block(out)
+            return self.conv_block(out, head=head)
         if self.attention:
             # `out` and `skip` each feed the gate AND the convolution block: the block side reads the alias the gate's 1x1
             # convolution publishes of its input, so the two gradients are summed in that convolution's backward-data epilogue
@@ -99,7 +105,7 @@ class UpsampleBlock(nn.Module):  # layers.py:131-168
             r = ops.AddReluFn.apply(o, sk)
             gate = self.psi(r, act=ops.ACT_SIGMOID)
             skip = ops.GateMulFn.apply(skip, gate)
-        return self.conv_block(out, skip)
+        return self.conv_block(out, skip, head=head)
 
 
 class PPM(nn.Module):  # layers.py:6-29
@@ -188,7 +194,15 @@ class OutputBlock(nn.Module):  # layers.py:171-189; NHWC features in, NCHW logit
         else:
             self.conv = nn.Conv2d(in_channels, nclass, kernel_size=1)
 
-    def forward(self, x):
+    def absorbable_head(self):
+        """the 1x1 convolution the layer in front may evaluate itself (ConvLayer.forward(head=...)): <= 4 NCHW logits straight from
+        the features; --interpolate resamples 4-padded NHWC logits instead"""
+        return self.conv if (not self.interpolate and self.conv.out_channels <= 4) else None
+
+    def forward(self, x, is_logits=False):
+        """is_logits: x is already self.conv's output (absorbable_head)"""
+        if is_logits:
+            return x + self.bias if self.coral_loss else x
         if not self.interpolate:
             out = xnn.head_conv(self.conv, x, nchw_out=True)
             return out + self.bias if self.coral_loss else out

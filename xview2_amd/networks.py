@@ -10,6 +10,7 @@ raises TypeError at construction.
 """
 import os
 
+import torch
 from torch import nn
 
 from . import nn as xnn
@@ -46,14 +47,17 @@ def get_decoder(encf, dilation, attn, no_skip=False, dec_interp=False):  # unet.
     return (DECF, *blocks)
 
 
-def _decode(owner, dilation, no_skip, encs, prefix="dec_l%d"):
-    """the dilation==1/2/4 branches of unet.py:150-170 as one loop over the existing decoder levels"""
+def _decode(owner, dilation, no_skip, encs, prefix="dec_l%d", head=None):
+    """the dilation==1/2/4 branches of unet.py:150-170 as one loop over the existing decoder levels.
+    head (OutputTemplate.absorbable_head): the 1x1 convolution that is the ONLY consumer of the last level's output - that level
+    evaluates it and the first return value is its logits, not dec5."""
     x, decs = encs[4], {}
     for lvl in range(_FIRST_LEVEL[dilation], 5):
         skip = None if (no_skip or lvl == 4) else encs[3 - lvl]
         # the previous level's output also feeds a deep-supervision head (unet.py:193-197): the head reads the alias this level's
         # transposed convolution publishes of its input (xnn.stage_with_input_alias)
-        x, alias = xnn.stage_with_input_alias(getattr(owner, prefix % (lvl + 1)), x, skip)
+        kw = {"head": head} if (head is not None and lvl == 4) else {}
+        x, alias = xnn.stage_with_input_alias(getattr(owner, prefix % (lvl + 1)), x, skip, **kw)
         if lvl - 1 in decs:
             decs[lvl - 1] = alias
         decs[lvl] = x
@@ -96,15 +100,17 @@ class UNetTemplate(nn.Module, _EncoderMixin):  # unet.py:113-172; takes/returns 
             self.dec_chn, self.dec_l1, self.dec_l2, self.dec_l3, self.dec_l4, self.dec_l5 = get_decoder(
                 self.enc_chn, self.dilation, args.attention, self.no_skip, args.dec_interp)
 
-    def forward(self, data):
+    def forward(self, data, head=None):
+        """head: see _decode (the caller's OutputTemplate consumes the first return value and nobody else does)"""
         encs = self._encode(data)
         if self.use_ppm:
             encs[4] = self.ppm(encs[4])
         elif self.use_aspp:
             encs[4] = self.aspp(encs[4])
         if self.interpolate:
+            assert head is None
             return encs[4], None, None
-        return _decode(self, self.dilation, self.no_skip, encs)
+        return _decode(self, self.dilation, self.no_skip, encs, head=head)
 
 
 class OutputTemplate(nn.Module):  # unet.py:175-197
@@ -121,8 +127,18 @@ class OutputTemplate(nn.Module):  # unet.py:175-197
             self.output_block_ds4 = OutputBlock(d4, n_class, interp)
         self.output_block = OutputBlock(d5, n_class, interp)
 
-    def forward(self, dec5, dec4, dec3):
-        out = self.output_block(dec5)
+    def absorbable_head(self, last_stage):
+        """the head convolution that `last_stage` (the decoder level producing dec5) may evaluate inside its last layer's BatchNorm
+        passes, so that dec5 never reaches HBM - or None.  For callers whose dec5 comes straight out of that one stage and feeds
+        nothing else; a training step only (gradients on, one BatchNorm batch), and nobody may watch dec5 go by: a forward hook on
+        the stage or on the output block is a second consumer."""
+        if (last_stage is None or not self.training or self.interp or not ops.HEAD_FUSE or not torch.is_grad_enabled()
+                or ops.BN_SPLIT != 1 or xnn.observed(last_stage, self)):
+            return None
+        return self.output_block.absorbable_head()
+
+    def forward(self, dec5, dec4, dec3, dec5_is_logits=False):
+        out = self.output_block(dec5, dec5_is_logits)
         if self.training and self.deep_supervision:
             return [out, self.output_block_ds4(dec4), self.output_block_ds3(dec3)]
         return out
@@ -144,7 +160,8 @@ class UNetLoc(nn.Module):  # unet.py:200-215
                                            interp=args.interpolate, enc_last=self.unet.enc_chn[-1])
 
     def forward(self, data):
-        return self.output_block(*self.unet(xnn.to_nhwc_image(data)))
+        head = self.output_block.absorbable_head(getattr(self.unet, "dec_l5", None))
+        return self.output_block(*self.unet(xnn.to_nhwc_image(data), head=head), dec5_is_logits=head is not None)
 
 
 class SiameseUNet(nn.Module):  # unet.py:218-236 (shared weights, BN statistics per pass)
@@ -201,7 +218,8 @@ class SiameseEncUNet(nn.Module, _EncoderMixin):  # unet.py:239-317
         else:
             pre, post = self.forward_enc(_pre(data)), self.forward_enc(_post(data))
             encs = [concat(a, b) for a, b in zip(pre, post)]
-        return self.output_block(*_decode(self, self.dilation, self.no_skip, encs))
+        head = self.output_block.absorbable_head(getattr(self, "dec_l5", None))
+        return self.output_block(*_decode(self, self.dilation, self.no_skip, encs, head=head), dec5_is_logits=head is not None)
 
 
 class _Fused(nn.Module, _EncoderMixin):
@@ -270,7 +288,8 @@ class FusedEncUNet(_Fused):  # unet.py:379-427
 
     def forward(self, data):
         f = self._encode_pair(data)
-        return self.output_block(*_decode(self, 1, False, [p[1] for p in f]))
+        head = self.output_block.absorbable_head(getattr(self, "dec_l5", None))
+        return self.output_block(*_decode(self, 1, False, [p[1] for p in f], head=head), dec5_is_logits=head is not None)
 
 
 class ParallelUNet(nn.Module):  # unet.py:430-446
@@ -314,7 +333,8 @@ class ParallelEncUNet(nn.Module, _EncoderMixin):  # unet.py:449-537
         if self.interpolate:
             return self.output_block(concat(pre[4], post[4]), None, None)
         encs = [concat(a, b) for a, b in zip(pre, post)]
-        return self.output_block(*_decode(self, self.dilation, self.no_skip, encs))
+        head = self.output_block.absorbable_head(getattr(self, "dec_l5", None))
+        return self.output_block(*_decode(self, self.dilation, self.no_skip, encs, head=head), dec5_is_logits=head is not None)
 
 
 class DiffUNet(nn.Module):  # unet.py:540-548

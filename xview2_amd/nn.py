@@ -7,6 +7,7 @@ Activations are NHWC.
 """
 import torch
 from torch import nn
+from torch.nn.modules import module as _torch_module
 
 from . import ops
 
@@ -83,6 +84,35 @@ def conv_bn_act(conv, bn, x0, x1=None, act=ops.ACT_NONE, residual=None, passthro
     return out
 
 
+def conv_bn_act_head(conv, bn, head, x0, x1=None, act=ops.ACT_NONE, nchw_out=True):
+    """head(act(BN(conv(cat(x0, x1))))) for a 1x1 `head` convolution that is the layer's ONLY consumer: one autograd node that never
+    stores the layer's activated output (ops.ConvBnActHeadFn) where ops.head_fusable() allows it, else the two nodes it replaces."""
+    cfg = _cfg(conv)
+    bs = ops.BnState(bn, SYNC_BN)
+    if not ops.head_fusable(x0, x1, conv._parameters["weight"], cfg, bs, head._parameters["weight"], bn.training):
+        return head_conv(head, conv_bn_act(conv, bn, x0, x1, act=act), nchw_out=nchw_out)
+    bump_bn_counter(bn)
+    return ops.ConvBnActHeadFn.apply(x0, x1, conv._parameters["weight"], bs.weight, bs.bias, head._parameters["weight"],
+                                     head._parameters["bias"], cfg, bs, act, nchw_out)
+
+
+def observed(*mods):
+    """does anything watch these modules (or their children) from outside - a forward (pre-)hook, on them or global?  Such a module's
+    inputs and outputs have a consumer the graph does not show."""
+    if getattr(_torch_module, "_global_forward_hooks", None) or getattr(_torch_module, "_global_forward_pre_hooks", None):
+        return True
+    for m in mods:
+        if m is None:
+            continue
+        subs = m.__dict__.get("_xv2_submodules")      # (the module tree of a built network does not change: walked once)
+        if subs is None:
+            subs = m.__dict__["_xv2_submodules"] = tuple(m.modules())
+        for c in subs:
+            if getattr(c, "_forward_hooks", None) or getattr(c, "_forward_pre_hooks", None):
+                return True
+    return False
+
+
 def _with_aliases(z, x0, x1, passthrough):
     if passthrough == 3:
         return z, x0, x1
@@ -146,16 +176,16 @@ class Chain(Numbered):
 # input; the other consumers read the alias, their gradient reaches the block's first layers as `dpass` and is summed in the
 # backward-data epilogue / pooling backward.  Blocks keep returning a single tensor (forward hooks, nn.Sequential semantics):
 # the alias travels through two attributes of the block.
-def stage_with_input_alias(stage, x, *more):
-    """-> (stage(x, *more), tensor that x's OTHER consumers should read): the alias published by the stage's first block, or x"""
+def stage_with_input_alias(stage, x, *more, **kw):
+    """-> (stage(x, *more, **kw), tensor that x's OTHER consumers should read): the alias published by the stage's first block, or x"""
     first = stage
     while isinstance(first, Chain) and len(first) > 0:
         first = first[0]
     if not (want_aliases(x) and hasattr(first, "alias_request")):
-        return stage(x, *more), x
+        return stage(x, *more, **kw), x
     first.alias_request = True
     try:
-        y = stage(x, *more)
+        y = stage(x, *more, **kw)
     finally:
         first.alias_request = False
     alias, first.alias_out = first.alias_out, None

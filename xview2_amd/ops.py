@@ -667,10 +667,12 @@ def _persist(tag, nfloats, device):
     return t
 
 
-def _conv_bn_act_train(x0, x1, weight, g, bn, residual, act, ihwo_out, want_mask, amax=None, want_gap=False):
+def _conv_bn_act_train(x0, x1, weight, g, bn, residual, act, ihwo_out, want_mask, amax=None, want_gap=False, head=None):
     """Training-mode conv + BatchNorm + (residual) + activation of one ungrouped layer as ONE ABI call
     (xv2_conv_bn_act_forward = the three launches of _conv_forward + _bn_forward, same order, same stream).
-    Returns y, z, zmask, (mean, invstd, count, scale, shift), or None when the shape has to go op by op."""
+    Returns y, z, zmask, (mean, invstd, count, scale, shift), or None when the shape has to go op by op.
+    head = (w [Cout_h, Cout], bias or None, nchw_out): the <= 4-channel head behind the layer is evaluated by the apply pass
+    (xv2_conv_bn_act_head_forward); z is never stored and the second return value is the logits."""
     N, IH, IW, C0t = x0.shape
     C1t = x1.shape[3] if x1 is not None else 0
     Cout = weight.shape[0]
@@ -682,6 +684,8 @@ def _conv_bn_act_train(x0, x1, weight, g, bn, residual, act, ihwo_out, want_mask
     if rgb and STEM_BAND and ihwo_out is None and 5 <= g.kw <= 8 and g.stride == 2 and g.dil == 1 and half:
         return None      # the RGB stem runs as a band convolution (_conv_forward)
     G = g.groups
+    if head is not None and (G > 1 or residual is not None or rgb):
+        return None
     if G > 1:
         # grouped layer (ResNeSt's radix convolution): the groups' launches behind ONE call (xv2_conv_bn_act_forward_grouped)
         if x1 is not None or rgb or not GROUPED_CALLS:
@@ -706,7 +710,7 @@ def _conv_bn_act_train(x0, x1, weight, g, bn, residual, act, ihwo_out, want_mask
             ihwo_out.append(ihwo)
     dev = x0.device
     y = _act((N, OH, OW, Cout), x0, torch.bfloat16 if half else torch.float32)
-    z = torch.empty_like(y)
+    z = torch.empty_like(y) if head is None else None
     sums = torch.empty((Cout, 2), dtype=torch.float64, device=dev)
     blob = _f32((4, Cout), x0)                                   # mean, invstd, scale, shift
     part = _persist("stats", tiles * Cout * 2, dev)      # (grouped: both groups' partials in one launch are rows of all Cout channels)
@@ -721,6 +725,16 @@ def _conv_bn_act_train(x0, x1, weight, g, bn, residual, act, ihwo_out, want_mask
         set_amax(amax[0], amax[1], None, amax[2][0] if amax[2] is not None else None)
         if amax[2] is not None:
             z._xv2_amax = amax[2]
+    if head is not None:
+        hw2, hbias, nchw_out = head
+        co = hw2.shape[0]
+        logits = _f32((N, co, OH, OW) if nchw_out else (N, OH, OW, co), x0)
+        call("xv2_conv_bn_act_head_forward", d, x0, C0t, x1, C1t, ohwi, y, Cout, part,
+             _persist("splitk", (wsb + 3) // 4 + 4, dev) if wsb else None,
+             sums, _stats_scratch(Cout, dev), float(npix), bn.weight, bn.bias, float(bn.eps), float(bn.momentum),
+             bn.running_mean, bn.running_var, blob[0], blob[1], blob[2], blob[3], act, co, hw2, hbias, logits,
+             1 if nchw_out else 0, _dt(y))
+        return y, logits, None, (blob[0], blob[1], float(npix), blob[2], blob[3])
     if G > 1:
         warr = (ctypes.c_void_p * G)(*[pk[0].data_ptr() for pk in packs])
         gap_part = None
@@ -1340,6 +1354,105 @@ class ConvBnActFn(torch.autograd.Function):
         ctx.wparam = None
         return (dx0, dx1, dw, dgamma if ctx.needs_input_grad[3] else None,
                 dbeta if ctx.needs_input_grad[4] else None, dres, None, None, None, None, None)
+
+
+HEAD_FUSE = os.environ.get("XV2_HEAD_FUSE", "1") != "0"      # the last decoder layer's head inside its BatchNorm passes (include/xv2.h)
+
+
+def head_fusable(x0, x1, weight, g, bn, head_weight, training):
+    """Can conv -> BatchNorm -> activation -> <= 4-channel 1x1 head run as ConvBnActHeadFn?  Training mode with one BatchNorm
+    batch in one process (no BN_SPLIT, no SyncBatchNorm exchange), the layer-level call available for the convolution's shape,
+    and a shape the fused kernels take (xv2_bn_act_head_supported)."""
+    if not (HEAD_FUSE and LAYER_CALLS and training and torch.is_grad_enabled() and BN_SPLIT == 1 and x0.is_cuda and g.groups == 1):
+        return False
+    if _sync_group(bn) or bn.weight is None or bn.bias is None or bn.running_mean is None or bn.running_var is None:
+        return False
+    if tuple(head_weight.shape[2:]) != (1, 1) or head_weight.shape[1] != weight.shape[0]:
+        return False
+    N, IH, IW, C0t = x0.shape
+    if C0t == 4 and x1 is None:      # (an RGB stem is no decoder layer)
+        return False
+    C1t = x1.shape[3] if x1 is not None else 0
+    OH, OW = _out_hw(IH, IW, g)
+    if query("xv2_bn_act_head_supported", N * OH * OW, weight.shape[0], head_weight.shape[0]) != 1:
+        return False
+    d = _desc(N, IH, IW, C0t, C1t, weight.shape[0], g, OH, OW, x0.dtype == torch.bfloat16)
+    return query("xv2_conv2d_forward_stats_tiles", d) > 0
+
+
+class ConvBnActHeadFn(torch.autograd.Function):
+    """logits = head(act(BN(conv(cat(x0, x1), W)))): the last decoder ConvLayer (model/layers.py:89-100) and the <= 4-channel 1x1
+    head behind it (OutputBlock, model/layers.py:171-189) as ONE autograd node.  The layer's activated output and the head's
+    input gradient - the two largest tensors of the step - are never stored: the BatchNorm apply pass evaluates the head, both
+    BatchNorm backward passes rebuild the gradient per element (xv2_conv_bn_act_head_forward / xv2_bn_act_head_backward).
+    Callers check head_fusable() first."""
+
+    @staticmethod
+    def forward(ctx, x0, x1, weight, gamma, beta, head_weight, head_bias, g, bn, act, nchw_out):
+        _need_cuda(x0)
+        ctx.set_materialize_grads(False)
+        x0_in, x1_in = x0, x1
+        x0 = x0.contiguous()
+        x1 = x1.contiguous() if x1 is not None else None
+        need_dx = x0.requires_grad or (x1 is not None and x1.requires_grad)
+        ctx.ihwo = [] if need_dx else None
+        am_in = None
+        if _amax_active(x0):      # F16X2: the sources' maxima; no slot for the output - no convolution reads it
+            am_in = (getattr(x0_in, "_xv2_amax", None), getattr(x1_in, "_xv2_amax", None) if x1_in is not None else None)
+        ctx.am_in = am_in
+        ctx.want_dx_amax = am_in is not None and bool(getattr(x0_in, "_xv2_convT_out", False))
+        co, C = head_weight.shape[0], weight.shape[0]
+        w2 = head_weight.reshape(co, C).contiguous()
+        fast = _conv_bn_act_train(x0, x1, weight, g, bn, None, act, ctx.ihwo, False,
+                                  (_tok_ptr(am_in[0]), _tok_ptr(am_in[1]), None) if am_in is not None else None,
+                                  head=(w2, head_bias, nchw_out))
+        if fast is None:
+            raise RuntimeError("ConvBnActHeadFn: no layer-level call for this shape (head_fusable() decides before the node is built)")
+        y, logits, _, stats = fast
+        ctx.save_for_backward(x0, x1, weight, gamma, y, w2, stats[0], stats[1], stats[3], stats[4])
+        ctx.count, ctx.g, ctx.bn, ctx.act, ctx.nchw = stats[2], g, bn, act, nchw_out
+        ctx.wparam, ctx.hparams, ctx.hshape = weight, (head_weight, head_bias), head_weight.shape
+        return logits
+
+    @staticmethod
+    def backward(ctx, dl):
+        x0, x1, weight, gamma, y, w2, mean, invstd, scale, shift = ctx.saved_tensors
+        g, bn = ctx.g, ctx.bn
+        N, H, W, C = y.shape
+        co = w2.shape[0]
+        npix = N * H * W
+        if dl is None:
+            dl = torch.zeros((N, co, H, W) if ctx.nchw else (N, H, W, co), dtype=torch.float32, device=y.device)
+        dl = dl.float().contiguous()
+        pw, pb = ctx.hparams
+        ctx.hparams = None
+        dhw = _grad_like(pw).view(co, C) if pw.is_contiguous() else torch.empty_like(w2)
+        dhb = _grad_like(pb) if pb is not None else None
+        dgamma, dbeta = _grad_like(bn.weight), _grad_like(bn.bias)
+        sums2 = torch.empty((C, 2), dtype=torch.float64, device=y.device)
+        ws = _persist("bnhead", (query("xv2_bn_act_head_backward_workspace", npix, C, co) + 3) // 4 + 4, y.device)
+        dy = torch.empty_like(y)
+        am_in = ctx.am_in
+        tok = _amax_new(y) if am_in is not None else None
+        if tok is not None:        # F16X2: the second pass records max |dy|
+            set_amax(None, None, None, tok[0])
+            dy._xv2_amax = tok
+        call("xv2_bn_act_head_backward", dl, 1 if ctx.nchw else 0, H * W, w2, co, y, C, mean, invstd, gamma, scale, shift,
+             ctx.act, float(ctx.count), dy, C, npix, C, sums2, dgamma, dbeta, dhw, dhb, ws, _dt(y))
+        am_dy = _amax_ptr(dy)
+        dx0 = dx1 = None
+        if ctx.needs_input_grad[0] or (x1 is not None and ctx.needs_input_grad[1]):
+            dx0, dx1 = _conv_backward_data(dy, weight, g, x0.shape[:3], x0.shape[3], x1.shape[3] if x1 is not None else 0,
+                                           ctx.ihwo, None, None, am_dy,
+                                           _amax_new(y) if (ctx.want_dx_amax and am_dy is not None) else None)
+        ctx.ihwo = None
+        dw = None
+        if ctx.needs_input_grad[2]:
+            wam = (_tok_ptr(am_in[0]), _tok_ptr(am_in[1]), am_dy) if (am_dy is not None and am_in is not None) else None
+            dw = _conv_backward_weight(x0, x1, dy, weight, g, ctx.wparam, wam)
+        ctx.wparam = None
+        return (dx0, dx1, dw, dgamma if ctx.needs_input_grad[3] else None, dbeta if ctx.needs_input_grad[4] else None,
+                dhw.reshape(ctx.hshape), dhb, None, None, None, None)
 
 
 class ConvFn(torch.autograd.Function):
