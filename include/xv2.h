@@ -612,6 +612,21 @@ int xv2_prof_record(int i, int* kid, double* ms, double* flops, double* algorith
 int xv2_augment_u8(const void* params, const void* src_img, const void* src_mask, const uint8_t* luts, int N, int C,
                    int h, int w, uint8_t* img, uint8_t* mask, void* stream);
 
+/* A.RandomScale(p=0.2, scale_limit=(0, 0.3), interpolation=INTER_CUBIC) of the same recipe (data_loading/pytorch_loader.py:57-63;
+ * this project's worker path resizes with Pillow: pytorch_loader.apply_scale) for the Z zoomed samples of a batch in ONE launch:
+ * the [y0:y0+h, x0:x0+w] window of the bicubic-resized tile and of the nearest-resized mask, the one-off sources of the
+ * xv2_augment_u8 call that follows.  The twin is of PILLOW's uint8 resampler: integer arithmetic on 22-bit fixed-point
+ * coefficients, horizontal pass -> round, clip to uint8 -> vertical pass -> round, clip; only the coefficient tables are
+ * floating point (fp64) and the host builds them (xview2_amd.data_loading.device_aug.resample_tables / nearest_table).
+ * params: [Z][8] int32 in device memory = {src, H, W, xoff, yoff, nxoff, nyoff, 0}: row of the pointer tables, source tile
+ * size and the offsets (in int32 elements) of the sample's tables in `tables`: at xoff [w][7] = {start, count, k[5]} of the
+ * window's columns, at yoff [h][7] of its rows (source index of the first tap, number of taps <= 5, coefficients * 2^22),
+ * at nxoff [w] / nyoff [h] the mask's nearest source column / row.  Up-scaling only (count <= 4 unclamped, a 32-row tile
+ * reads <= 36 source rows).  src_img / src_mask as in xv2_augment_u8; outputs img [Z][h][w][C], mask [Z][h][w]; C = 3 or 6.
+ * Bit-exact against device_aug.zoom_crop_numpy and Pillow (tests/test_zoom_cpu.py, tests/test_zoom_gpu.py). */
+int xv2_zoom_crop_u8(const void* params, const int32_t* tables, const void* src_img, const void* src_mask, int Z, int C,
+                     int h, int w, uint8_t* img, uint8_t* mask, void* stream);
+
 /* ---- SyncBatchNorm statistics exchange without a collective library call ------------------------------------------
  * (reference: Trainer(sync_batchnorm=gpus > 1), main.py:106 - torch.nn.SyncBatchNorm exchanges <= 32 KB per BatchNorm
  * layer and direction, 126 ... 606 times per step).  Every rank allocates one exchange buffer (xv2_xchg_alloc returns
