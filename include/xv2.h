@@ -627,6 +627,28 @@ int xv2_augment_u8(const void* params, const void* src_img, const void* src_mask
 int xv2_zoom_crop_u8(const void* params, const int32_t* tables, const void* src_img, const void* src_mask, int Z, int C,
                      int h, int w, uint8_t* img, uint8_t* mask, void* stream);
 
+/* `--autoaugment` (data_loading/autoaugment.py ImageNetPolicy; this project's worker path runs it through Pillow:
+ * xview2_amd/data_loading/autoaugment.py) for the N cropped samples of a batch, IN PLACE on img [N][h][w][C] and mask [N][h][w] -
+ * the outputs of an xv2_augment_u8 call without flips, noise or tables.  Every sample runs the 0 .. 2 operations the host drew
+ * for it (autoaugment.draw_policy), stage 2 on stage 1's output; the twin is of PILLOW's bytes for the ten operations of the
+ * POLICY table: posterize / solarize / invert (host-built 256-byte tables), autocontrast / equalize (tables built on the device
+ * from per-channel histograms: integer counts, equalize in integers, autocontrast one fp64 multiply and add per entry), color /
+ * contrast / sharpness (Image.blend in float32 against L, the rounded mean of L, ImageFilter.SMOOTH), rotate (NEAREST gather
+ * in 16.16 fixed point, zero fill, image and mask) and shearX (BICUBIC in fp64, zero fill, image AND mask: the reference
+ * interpolates labels).  The same operation runs on each 3-channel part in STORED channel order, on the mask only if geometric.
+ * params: [N][2][8] int32 in device memory, per sample and stage {op, a[6], 0}: op 0 none, 1 host-built table, 2 autocontrast,
+ * 3 equalize, 4 color, 5 contrast, 6 sharpness (a[0] = bits of the float32 factor 1 + magnitude * sign), 7 rotate (a[0..5] =
+ * the fixed-point coefficients a0 .. a5 of Geometry.c affine_fixed), 8 shearX (a[1], a[2] = low and high word of the fp64
+ * coefficient); host_params: the same table in HOST memory - it is validated (unknown ids are rejected) and decides which
+ * launches a stage needs, the device never reports back; luts: [N][2][256] uint8 in device memory, the table of (sample, stage)
+ * where op = 1 (NULL if no sample has one).  Per stage at most a statistics, a table and an apply launch, ordered by `stream`
+ * alone; nothing is enqueued when no sample has an operation.  workspace: xv2_autoaugment_workspace(N, C, h, w) bytes (histograms,
+ * sums, tables and one copy of the batch: a gather cannot run in place), 0 for arguments the entry point rejects.  C = 3 or 6,
+ * h * w <= 2^24.  Bit-exact against device_autoaug.autoaug_numpy and Pillow (tests/test_autoaug_cpu.py, tests/test_autoaug_gpu.py). */
+size_t xv2_autoaugment_workspace(int N, int C, int h, int w);
+int xv2_autoaugment_u8(const int32_t* host_params, const void* params, const uint8_t* luts, int N, int C, int h, int w,
+                       uint8_t* img, uint8_t* mask, void* workspace, void* stream);
+
 /* ---- SyncBatchNorm statistics exchange without a collective library call ------------------------------------------
  * (reference: Trainer(sync_batchnorm=gpus > 1), main.py:106 - torch.nn.SyncBatchNorm exchanges <= 32 KB per BatchNorm
  * layer and direction, 126 ... 606 times per step).  Every rank allocates one exchange buffer (xv2_xchg_alloc returns

@@ -14,7 +14,18 @@ Kernel durations from the trace (same batches; the device branch only, so that t
     timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- \
         python scripts/bench_loader.py --modes post --probs 1.0 --zoom device
 The trace also holds the untimed first epoch (tiles / batch launches of xv2_augment_u8 at the real zoom probability, with the
-few xv2_zoom_crop_u8 launches that draws): with the default 6 timed epochs that is 1 augment launch in 7."""
+few xv2_zoom_crop_u8 launches that draws): with the default 6 timed epochs that is 1 augment launch in 7.
+
+`--autoaugment` runs another leg INSTEAD: batches per second of `--autoaugment` through the worker pipeline (DataLoader workers:
+decode, crop, two PIL operations per image, upload - what DataModule builds by default) against the device path
+(DeviceAugLoader(autoaugment=True): xv2_augment_u8 + xv2_autoaugment_u8, XV2_DEVICE_AUTOAUGMENT=1), same tile tree, same
+`--num_workers` (worker processes there, decode threads here), for pre and post in one run:
+
+    python scripts/bench_loader.py --autoaugment [--num_workers 8] [--tiles 32] [--batch 16] [--epochs 6] [--modes pre,post]
+
+Timed: whole epochs on the consuming thread, a device synchronise after each batch (a training step would overlap it); the two
+paths alternate epoch by epoch.  The worker path decodes its tiles every epoch and starts its workers every epoch - that is the
+pipeline as it runs; the device path's first epoch (decode + upload into the HBM cache) is reported on its own line."""
 import argparse
 import json
 import os
@@ -84,6 +95,44 @@ def run(loader, epochs, prob, variants, seed=11):
     return {v: out[v] + (zoomed[v],) for v in variants}
 
 
+def _epoch(loader):
+    """-> (batches, seconds) of one epoch, the device drained after every batch"""
+    t0, n = time.perf_counter(), 0
+    for b in loader:
+        torch.cuda.synchronize()
+        n += 1
+    return n, time.perf_counter() - t0
+
+
+def autoaugment_leg(root, a):
+    rows = []
+    for mode in a.modes.split(","):
+        path = os.path.join(root, "train")
+        kwargs = {"batch_size": a.batch, "pin_memory": True, "num_workers": a.num_workers, "drop_last": True, "shuffle": True}
+        worker = dm._OnDevice(pl.fetch_pytorch_loader(path, mode, True, kwargs, True, True), "cuda:0")
+        ds = pl.fetch_pytorch_loader(path, mode, True, {"batch_size": 1}, False, True).dataset
+        device = dm.DeviceAugLoader(ds, a.batch, "cuda:0", seed=3, threads=max(2, a.num_workers), autoaugment=True)
+        device.set_epoch(0)
+        n, first = _epoch(device)       # decode + upload every tile once
+        tot = {"worker": [0, 0.0], "device": [0, 0.0]}
+        for epoch in range(1, a.epochs + 1):
+            device.set_epoch(epoch)
+            for name, loader in (("worker", worker), ("device", device)):
+                n, t = _epoch(loader)
+                tot[name][0] += n
+                tot[name][1] += t
+        row = {"mode": mode, "batch": a.batch, "num_workers": a.num_workers, "epochs": a.epochs,
+               "batches_per_epoch": tot["device"][0] // a.epochs,
+               "device_first_epoch_batches_per_s": round(n / first, 2),
+               "worker_batches_per_s": round(tot["worker"][0] / tot["worker"][1], 2),
+               "device_batches_per_s": round(tot["device"][0] / tot["device"][1], 2)}
+        rows.append(row)
+        print("%-4s --autoaugment: worker pipeline (%d workers) %.2f batches / s, device path %.2f batches / s (its decoding first "
+              "epoch: %.2f); batches of %d" % (mode, a.num_workers, row["worker_batches_per_s"], row["device_batches_per_s"],
+                                               row["device_first_epoch_batches_per_s"], a.batch), flush=True)
+    return rows
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--tiles", type=int, default=32)
@@ -92,10 +141,15 @@ def main():
     p.add_argument("--modes", default="pre,post")
     p.add_argument("--probs", default="1.0,0.2")
     p.add_argument("--zoom", default="device,host")
+    p.add_argument("--autoaugment", action="store_true", help="the --autoaugment leg instead: worker pipeline against device path")
+    p.add_argument("--num_workers", type=int, default=8)
     a = p.parse_args()
     rows = []
     with tempfile.TemporaryDirectory() as root:
         pl.DEFAULT_INDEX = tile_tree(root, a.tiles)
+        if a.autoaugment:
+            print(json.dumps({"device": torch.cuda.get_device_name(0), "autoaugment_rows": autoaugment_leg(root, a)}))
+            return
         for mode in a.modes.split(","):
             ds = pl.fetch_pytorch_loader(os.path.join(root, "train"), mode, True, {"batch_size": 1}, False, True).dataset
             loader = dm.DeviceAugLoader(ds, a.batch, "cuda:0", seed=3, threads=4)

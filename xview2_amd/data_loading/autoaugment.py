@@ -79,6 +79,20 @@ def apply_op(img, op, mag, sign, fillcolor=0):
     raise ValueError("unknown AutoAugment operation %r" % op)
 
 
+def draw_policy(rng):
+    """the DECISIONS of one ImageNetPolicy call: [(op, magnitude, sign)], 0 .. 2 entries - the sub-policy index, then per
+    operation its skip (`random() >= p`) and, when it runs, its sign (`random() < 0.5`; rotate ignores it, it is drawn all the
+    same).  The one statement of the stream: ImageNetPolicy.__call__ applies these through PIL, the device path
+    (device_autoaug.py, include/xv2.h xv2_autoaugment_u8) on the GPU"""
+    p1, op1, m1, p2, op2, m2 = POLICY[int(rng.integers(0, len(POLICY)))]
+    ops = []
+    for p, op, mi in ((p1, op1, m1), (p2, op2, m2)):
+        if rng.random() >= p:
+            continue
+        ops.append((op, magnitude(op, mi), (1 if rng.random() < 0.5 else -1)))
+    return ops
+
+
 class ImageNetPolicy:
     def __init__(self, fillcolor=0, rng=None):
         self.fillcolor = fillcolor
@@ -91,12 +105,7 @@ class ImageNetPolicy:
         return _rng()
 
     def __call__(self, img, lbl, img2=None):
-        r = self._rng()
-        p1, op1, m1, p2, op2, m2 = POLICY[int(r.integers(0, len(POLICY)))]
-        for p, op, mi in ((p1, op1, m1), (p2, op2, m2)):
-            if r.random() >= p:
-                continue
-            mag, sign = magnitude(op, mi), (1 if r.random() < 0.5 else -1)
+        for op, mag, sign in draw_policy(self._rng()):
             img = apply_op(img, op, mag, sign, self.fillcolor)
             if img2 is not None:
                 img2 = apply_op(img2, op, mag, sign, self.fillcolor)

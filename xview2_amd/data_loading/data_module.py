@@ -46,9 +46,18 @@ class DeviceAugLoader:
     cv2 INTER_CUBIC stays unpinned as before (VERDICT row f4).  XV2_DEVICE_ZOOM=0 is the host branch: the tile comes back
     from the cache, is zoomed and cropped by Pillow and uploaded.  It is the default: the same-run timing of the two branches
     on an MI355X that the default is to follow (scripts/bench_loader.py) is not recorded.  Sampling = DataLoader(shuffle=True, drop_last=True) /
-    DistributedSampler semantics."""
+    DistributedSampler semantics.
 
-    def __init__(self, dataset, batch_size, device, rank=0, world_size=1, seed=0, threads=4, shuffle=True):
+    autoaugment=True is `--autoaugment` on the device: per sample the host draws the crop (device_aug.draw_crop) and the 0 .. 2
+    operations of one ImageNet sub-policy (autoaugment.draw_policy) - the worker path's stream, in its order; no zoom, flips or
+    noise, as there - and a batch is the crop launch followed by ONE call (include/xv2.h xv2_autoaugment_u8) that runs every
+    sample's operations in place: a twin of the bytes PILLOW produces for the ten operations of the POLICY table
+    (device_autoaug.autoaug_numpy; tests/test_autoaug_cpu.py, tests/test_autoaug_gpu.py), no PIL operation runs on the host.
+    DataModule chooses it for `--autoaugment` only with XV2_DEVICE_AUTOAUGMENT=1; the default 0 keeps the worker pipeline:
+    one same-run timing of the two is recorded (scripts/bench_loader.py --autoaugment; DESIGN.md section 8,
+    profiles/r08_autoaugment_loader.md) and the change of the default is left to a change that cites it."""
+
+    def __init__(self, dataset, batch_size, device, rank=0, world_size=1, seed=0, threads=4, shuffle=True, autoaugment=False):
         from .device_aug import DeviceAugmenter, DeviceTileCache
         self.ds, self.bs, self.device = dataset, int(batch_size), torch.device(device)
         self.rank, self.world, self.seed, self.epoch, self.shuffle = rank, world_size, seed, 0, shuffle
@@ -56,6 +65,7 @@ class DeviceAugLoader:
         self.aug = DeviceAugmenter(self.cache)
         self.rows, self.host_masks = {}, {}
         self.threads = max(1, int(threads))
+        self.autoaugment = bool(autoaugment)
         # XV2_DEVICE_ZOOM=1: RandomScale on the device; 0 (the default, see the class docstring): on the host (Pillow); a cache in
         # host memory has no kernel to run
         self.device_zoom = os.environ.get("XV2_DEVICE_ZOOM", "0") != "0" and self.device.type == "cuda"
@@ -94,7 +104,8 @@ class DeviceAugLoader:
         import numpy as np
         from concurrent.futures import ThreadPoolExecutor
         from . import pytorch_loader as pl
-        from .device_aug import draw_params, nearest_table, zoomed_size
+        from .autoaugment import draw_policy
+        from .device_aug import crop_params, draw_crop, draw_params, nearest_table, zoomed_size
         from ..ops import DeviceImage
         if self.rng is None or self._rng_epoch != self.epoch:
             # a private stream per (seed, rank, epoch): follows --seed, differs between the ranks of a data-parallel job
@@ -118,6 +129,16 @@ class DeviceAugLoader:
                 # every cache row of the batch is resolved BEFORE a one-off tile gets its index: cache.add() of a later,
                 # not yet cached sample would otherwise shift len(cache) under an earlier zoomed sample's index
                 resolved = [self._row(i, pending) for i in order[b * self.bs:(b + 1) * self.bs]]
+                if self.autoaugment:     # crop + one sub-policy per sample: the crop launch, then xv2_autoaugment_u8
+                    policies = []
+                    for row, mask in resolved:
+                        y0, x0 = draw_crop(self.rng, mask)
+                        plist.append(crop_params(mask.shape[0], mask.shape[1], y0, x0, self.cache.imgs[row].shape[2] // 3))
+                        rows.append(row)
+                        policies.append(draw_policy(self.rng))
+                    img, mask = self.aug.autoaugment(plist, rows, policies)
+                    yield {"image": DeviceImage(img), "mask": mask}
+                    continue
                 base = len(self.cache)
                 zlist = []
                 for row, mask in resolved:
@@ -186,13 +207,17 @@ class DataModule:
 
     def train_dataloader(self):
         if getattr(self, "_train", None) is None:
-            # augmentation on the device, tiles resident in HBM (DeviceAugLoader); XV2_DEVICE_AUG=0, --autoaugment (a PIL policy)
-            # or the host-normalise switch keep the reference's worker pipeline
+            # augmentation on the device, tiles resident in HBM (DeviceAugLoader); XV2_DEVICE_AUG=0 or the host-normalise switch
+            # keep the reference's worker pipeline, and so does --autoaugment (a PIL policy) unless XV2_DEVICE_AUTOAUGMENT=1
+            # selects its device twin (default 0: DeviceAugLoader's docstring)
+            auto = bool(getattr(self.args, "autoaugment", False))
             if (self.raw_u8 and os.environ.get("XV2_DEVICE_AUG", "1") != "0" and
-                    not getattr(self.args, "autoaugment", False)):
+                    (not auto or os.environ.get("XV2_DEVICE_AUTOAUGMENT", "0") != "0")):
+                # (the dataset only decodes tiles here - load() / key() - so it is built without its PIL policy)
                 ds = fetch_pytorch_loader(self.train_path, self.args.type, True, {"batch_size": 1}, False, True).dataset
                 self._train = DeviceAugLoader(ds, self.args.batch_size, self.device, self.rank, self.world_size,
-                                              seed=getattr(self.args, "seed", 0) or 0, threads=max(2, self.args.num_workers))
+                                              seed=getattr(self.args, "seed", 0) or 0, threads=max(2, self.args.num_workers),
+                                              autoaugment=auto)
             else:
                 self._train = self._loader(self.train_path, True, self.train_loader_kwargs)
         return self._train

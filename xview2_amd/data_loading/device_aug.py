@@ -45,20 +45,28 @@ def hash_normal_field(seed, n, sigma):
     return (float(np.float32(sigma)) * g).astype(np.float32)
 
 
-def draw_params(rng, mask, parts, height=512, width=512):
-    """the random decisions of one sample, in pipeline order (pytorch_loader.py:77-91): crop, hflip, vflip, then per image the
-    noise, then per image brightness / contrast.  `mask`: the (possibly zoomed) uint8 mask, `parts`: 1 (pre) or 2 (pre | post)"""
+def draw_crop(rng, mask, height=512, width=512):
+    """A.CropNonEmptyMaskIfExists(p=1): -> (y0, x0) of a height x width window around a random foreground pixel of `mask`,
+    else of a random window.  The crop part of draw_params, and all of the crop that `--autoaugment` draws"""
     H, W = mask.shape[:2]
     if H < height or W < width:
         raise ValueError("crop %dx%d larger than the tile %dx%d" % (height, width, H, W))
     ys, xs = np.nonzero(mask)
-    if ys.size:       # A.CropNonEmptyMaskIfExists: a window around a random foreground pixel
+    if ys.size:
         k = int(rng.integers(0, ys.size))
         y0 = int(np.clip(ys[k] - rng.integers(0, height), 0, H - height))
         x0 = int(np.clip(xs[k] - rng.integers(0, width), 0, W - width))
     else:
         y0 = int(rng.integers(0, H - height + 1))
         x0 = int(rng.integers(0, W - width + 1))
+    return y0, x0
+
+
+def draw_params(rng, mask, parts, height=512, width=512):
+    """the random decisions of one sample, in pipeline order (pytorch_loader.py:77-91): crop, hflip, vflip, then per image the
+    noise, then per image brightness / contrast.  `mask`: the (possibly zoomed) uint8 mask, `parts`: 1 (pre) or 2 (pre | post)"""
+    H, W = mask.shape[:2]
+    y0, x0 = draw_crop(rng, mask, height, width)
     p = {"H": H, "W": W, "h": height, "w": width, "y0": y0, "x0": x0,
          "hflip": bool(rng.random() < 0.33), "vflip": bool(rng.random() < 0.33), "noise": [], "lut": []}
     for _ in range(parts):      # A.GaussNoise(p=0.1, var_limit=(10, 50)): one call per image
@@ -75,6 +83,12 @@ def draw_params(rng, mask, parts, height=512, width=512):
         else:
             p["lut"].append(None)
     return p
+
+
+def crop_params(H, W, y0, x0, parts, height=512, width=512):
+    """the parameters of a crop and nothing else (no flips, noise or tables): what `--autoaugment` asks of xv2_augment_u8"""
+    return {"H": H, "W": W, "h": height, "w": width, "y0": y0, "x0": x0, "hflip": False, "vflip": False,
+            "noise": [None] * parts, "lut": [None] * parts}
 
 
 def apply_params_numpy(img, mask, p):
@@ -268,6 +282,7 @@ class DeviceAugmenter:
 
     def __init__(self, cache):
         self.cache = cache
+        self._workspace = None
 
     def zoom(self, zlist, h=512, w=512):
         """[(cache row, factor, y0, x0)] -> [(uint8 [h, w, C], uint8 [h, w])] on the device: the crop windows of the zoomed tiles
@@ -311,4 +326,24 @@ class DeviceAugmenter:
         img = torch.empty((n, h, w, C), dtype=torch.uint8, device=dev)
         mask = torch.empty((n, h, w), dtype=torch.uint8, device=dev)
         call("xv2_augment_u8", torch.from_numpy(tab).to(dev), pi, pm, torch.from_numpy(luts).to(dev), n, C, h, w, img, mask)
+        return img, mask
+
+    def autoaugment(self, plist, rows, ops_list):
+        """`--autoaugment` for a batch: the crop launch (`plist`: device_aug.crop_params per sample), then every sample's 0 .. 2
+        policy operations (`ops_list`: autoaugment.draw_policy per sample) in place on the cropped batch - ONE parameter upload
+        and one call (include/xv2.h xv2_autoaugment_u8: at most three launches per stage, no statistic returns to the host)"""
+        import torch
+        from .._capi import Ptr, call, query
+        from .device_autoaug import ROW, pack_policy
+        if len(ops_list) != len(plist):
+            raise ValueError("%d policies for %d samples" % (len(ops_list), len(plist)))
+        img, mask = self(plist, rows)
+        n, h, w, C = img.shape
+        host = pack_policy(ops_list, h, w)              # (alive until the call returns: the entry point validates it)
+        buf = torch.from_numpy(host).to(self.cache.device)
+        need = query("xv2_autoaugment_workspace", n, C, h, w)
+        if self._workspace is None or self._workspace.numel() < need:
+            # kept between batches: every use is ordered behind the last one by the stream
+            self._workspace = torch.empty(need, dtype=torch.uint8, device=self.cache.device)
+        call("xv2_autoaugment_u8", host.ctypes.data, buf, Ptr(buf, n * 2 * ROW), n, C, h, w, img, mask, self._workspace)
         return img, mask
