@@ -579,6 +579,36 @@ int xv2_novograd_step_dev(const int64_t* rows, int64_t rows_total, const int64_t
                           const float* lr_dev, int* step_dev, double beta1, double beta2, float eps,
                           float weight_decay, float grad_scale, void* stream);
 
+/* Gradient guard: global-norm clipping (torch.nn.utils.clip_grad_norm_, PL's Trainer(gradient_clip_val)) and the skipping of a
+ * step whose gradient holds an Inf or NaN (what the reference's --precision 16 GradScaler does, main.py:99), decided on the
+ * device between the backward pass and any of the device-state rules above.
+ * xv2_grad_guard: two launches over grad[0 .. n) - the sum of squares in double (16-byte loads where `grad` is 16-byte
+ *   aligned, one double per block in `workspace` = xv2_grad_guard_workspace(n) bytes, a grid that depends on n alone, fixed
+ *   lane order and butterfly, no atomics: bitwise reproducible), then a one-block fold that adds the partials in index order
+ *   and writes `guard`, a 64-byte, 8-byte aligned record the caller zeroes ONCE and keeps for the run:
+ *     byte  0  float   norm              grad_scale * sqrt(sum), of this call (grad_scale: the reducer's 1 / world)
+ *     byte  4  float   coef              min(max_norm / (norm + 1e-6), 1), computed in double; 1 when max_norm == 0 (no clipping)
+ *     byte  8  int32   skip              1: skip_nonfinite != 0 and the norm is not finite
+ *     byte 12  int32   skipped_in_a_row  consecutive skipped calls up to and including this one
+ *     byte 16  int64   steps             calls so far          (these three accumulate)
+ *     byte 24  int64   clipped           calls with coef < 1 that were not skipped
+ *     byte 32  int64   skipped           calls with skip = 1
+ *     byte 40  float   norm_max          the largest finite norm so far
+ *     bytes 44 .. 63   reserved
+ *   With skip_nonfinite == 0 the formula is applied as it stands: an Inf norm gives coef 0, a NaN norm gives NaN, as in torch.
+ *   A finite fp32 squared cannot overflow a double, so the one reduction answers both questions.
+ * xv2_optim_guard_ctx(guard) names the record for the NEXT optimizer entry point of THIS host thread (xv2_adamw_step_dev,
+ *   xv2_flat_step_dev, xv2_adamp_step_dev, xv2_novograd_step_dev); it is cleared when that call returns, whatever it returns
+ *   (the lifetime of xv2_amax_ctx).  The call then runs the guarded instantiation of its kernels: the effective gradient scale
+ *   is grad_scale * coef, read from the device, and with skip = 1 every kernel returns before touching anything - parameters,
+ *   state arrays, decision / norm_avg and the step counter stay bit for bit (scaling the gradient to zero would not be a skip:
+ *   moments and weight decay would still move).  NULL, or no call: the kernels without a guard.  xv2_adamw_step takes its
+ *   step from the host and refuses a guard (XV2_EINVAL). */
+size_t xv2_grad_guard_workspace(int64_t n);
+int xv2_grad_guard(const float* grad, int64_t n, float grad_scale, float max_norm, int skip_nonfinite, void* workspace,
+                   void* guard, void* stream);
+int xv2_optim_guard_ctx(const void* guard);
+
 /* ---- in-library kernel timing (bench.py roofline leg) --------------------------------------
  * When enabled, every launch of an MFMA kernel (implicit-GEMM conv / weight-gradient) is bracketed
  * by hipEvents on its own stream and tagged with its algorithmic FLOP count (2*M*N*K of the

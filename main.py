@@ -66,6 +66,9 @@ _LAUNCH_FLAGS = [
                       help="localization checkpoint whose encoder initialises the damage model")),
     ("type", dict(type=str, choices=["pre", "post"], help="pre: building localization; post: damage assessment")),
     ("seed", dict(type=int, default=1)),
+    # PL Trainer(gradient_clip_val) and its native-AMP GradScaler's step skipping (not flags of the reference's main.py)
+    ("gradient_clip_val", dict(type=float, default=0.0, help="clip the global gradient norm to this value (0: off)")),
+    ("skip_nonfinite", dict(action="store_true", help="skip (and count) an optimizer step whose gradient holds Inf / NaN")),
     # synthetic-data knobs (not in the reference)
     ("train_size", dict(type=int, default=512)),
     ("eval_size", dict(type=int, default=1024)),
@@ -108,7 +111,8 @@ def main(argv=None):
     trainer = Trainer(gpus=args.gpus, precision=args.precision, max_epochs=args.epochs, min_epochs=args.epochs,
                       sync_batchnorm=args.gpus > 1, accelerator="ddp" if args.gpus > 1 else None,
                       default_root_dir=args.results, checkpoint_callback=args.exec_mode == "train",
-                      resume_from_checkpoint=checkpoint)
+                      resume_from_checkpoint=checkpoint, gradient_clip_val=args.gradient_clip_val,
+                      skip_nonfinite=args.skip_nonfinite)
     if args.data == "synthetic":
         dm = SyntheticDataModule(args, device=trainer.device, rank=trainer.rank, train_size=args.train_size,
                                  eval_size=args.eval_size, steps_per_epoch=args.steps_per_epoch)

@@ -7,6 +7,7 @@
 #include <vector>
 #include "../../include/xv2.h"
 #include "amax_ctx.h"
+#include "optim_ctx.h"
 
 namespace xv2 {
 AmaxCtx& amax_ctx() {
@@ -17,7 +18,16 @@ int& amax_depth() {
     static thread_local int d = 0;
     return d;
 }
+const float*& optim_guard_ctx() {
+    static thread_local const float* g = nullptr;
+    return g;
+}
 }  // namespace xv2
+
+extern "C" int xv2_optim_guard_ctx(const void* guard) {
+    xv2::optim_guard_ctx() = static_cast<const float*>(guard);
+    return 0;
+}
 
 extern "C" int xv2_amax_ctx(const void* amax_a0, const void* amax_a1, const void* amax_dy, void* amax_out) {
     xv2::AmaxCtx& c = xv2::amax_ctx();

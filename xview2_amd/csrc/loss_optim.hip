@@ -8,6 +8,7 @@
 // fp32 inside a thread, fp64 across threads/blocks, fixed order -> acc[] -> scalar loss.
 // Backward: a second streaming pass forms dL/dlogits analytically from acc[] (no autograd graph).
 #include "xv2_common.h"
+#include "optim_ctx.h"
 #include <algorithm>
 
 namespace xv2 {
@@ -430,10 +431,18 @@ __device__ __forceinline__ void adamw_one(float& p, float g, float& m, float& v,
     const float denom = sqrtf(vi) / bc2_sqrt + eps;
     p = pi - (lr / bc1) * (mi / denom);
 }
+// GUARDED (include/xv2.h "gradient guard"): the record's skip flag returns before anything is touched, its clip coefficient
+// multiplies the gradient scale; the other instantiation is the kernel without a guard
+template <bool GUARDED>
 __global__ void __launch_bounds__(256) adamw_dev_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                          float* __restrict__ m, float* __restrict__ v, int64_t n,
                                                          const float* __restrict__ lr_dev, float b1, float b2, float eps,
-                                                         float wd, const int* __restrict__ step_dev, float gscale) {
+                                                         float wd, const int* __restrict__ step_dev, float gscale,
+                                                         const float* __restrict__ guard) {
+    if (GUARDED) {
+        if (reinterpret_cast<const int*>(guard)[GUARD_SKIP] != 0) return;
+        gscale *= guard[GUARD_COEF];
+    }
     const float lr = lr_dev[0];
     const float step = (float)(step_dev[0] + 1);
     const float bc1 = 1.f - powf(b1, step);
@@ -456,7 +465,11 @@ __global__ void __launch_bounds__(256) adamw_dev_kernel(float* __restrict__ p, c
     for (int64_t i = n4 * 4 + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
         adamw_one(p[i], g[i], m[i], v[i], lr, b1, b2, eps, wd, bc1, bc2_sqrt, gscale);
 }
-__global__ void inc_i32_kernel(int* p) { p[0] += 1; }
+template <bool GUARDED>
+__global__ void inc_i32_kernel(int* p, const float* __restrict__ guard) {
+    if (GUARDED && reinterpret_cast<const int*>(guard)[GUARD_SKIP] != 0) return;     // a skipped step is not counted
+    p[0] += 1;
+}
 
 }  // namespace xv2
 
@@ -465,11 +478,20 @@ using namespace xv2;
 extern "C" int xv2_adamw_step_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
                                   const float* lr_dev, float beta1, float beta2, float eps, float weight_decay,
                                   int* step_dev, float grad_scale, void* stream) {
+    OptimGuardScope scope;          // (the guard named for this call, cleared on every way out)
+    const float* guard = scope.guard;
     const int grid = (int)std::min<int64_t>(cdiv(cdiv(n, 4), 256), 4096);
-    hipLaunchKernelGGL(adamw_dev_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg,
-                       exp_avg_sq, n, lr_dev, beta1, beta2, eps, weight_decay, step_dev, grad_scale);
+    if (guard)
+        hipLaunchKernelGGL(adamw_dev_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg,
+                           exp_avg_sq, n, lr_dev, beta1, beta2, eps, weight_decay, step_dev, grad_scale, guard);
+    else
+        hipLaunchKernelGGL(adamw_dev_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg,
+                           exp_avg_sq, n, lr_dev, beta1, beta2, eps, weight_decay, step_dev, grad_scale, guard);
     XV2_CHECK_LAUNCH();
-    hipLaunchKernelGGL(inc_i32_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, step_dev);
+    if (guard)
+        hipLaunchKernelGGL(inc_i32_kernel<true>, dim3(1), dim3(1), 0, (hipStream_t)stream, step_dev, guard);
+    else
+        hipLaunchKernelGGL(inc_i32_kernel<false>, dim3(1), dim3(1), 0, (hipStream_t)stream, step_dev, guard);
     XV2_CHECK_LAUNCH();
     return XV2_OK;
 }
@@ -610,6 +632,9 @@ extern "C" int xv2_pack_weights_table(const int64_t* table, int n, int64_t total
 extern "C" int xv2_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
                               float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale,
                               void* stream) {
+    OptimGuardScope scope;
+    // (a skipped step must not advance the step: only the device-counter forms can honour a guard)
+    XV2_CHECK_ARG(!scope.guard, "adamw_step: a gradient guard needs the device-state form (xv2_adamw_step_dev)");
     const float bc1 = 1.f - powf(beta1, (float)step);
     const float bc2 = 1.f - powf(beta2, (float)step);
     const int grid = (int)std::min<int64_t>(cdiv(n, 256), 4096);

@@ -9,12 +9,30 @@
 // the buffer into rows (dim 0 of a tensor with >= 2 dims, else the whole tensor).  One wave per row sums a row's
 // products into `partials` (a fixed lane-strided order and a fixed butterfly: no atomics, bitwise-reproducible steps),
 // one wave per tensor folds its rows in a fixed order, one wave per row applies the update.
+//
+// Gradient guard (xv2_grad_guard): two launches in front of any rule - a grid-stride sum of squares of the whole gradient
+// buffer in double (one partial per block, fixed lane order and butterfly), then a one-block fold that adds the partials in
+// index order and writes the guard record (include/xv2.h): the clipped global norm's coefficient and the skip flag of a
+// non-finite gradient.  Every rule kernel is a template on GUARDED: that form multiplies the gradient scale by the record's
+// coefficient and returns before touching anything when the record says skip; the other form is the code without a guard.
 #include "xv2_common.h"
+#include "optim_ctx.h"
 #include <algorithm>
+#include <cmath>
 
 namespace xv2 {
 
 enum FlatRule { RULE_SGD = 0, RULE_SGD_MOMENTUM = 1, RULE_RADAM = 2, RULE_ADABELIEF = 3, RULE_ADABOUND = 4 };
+
+// GUARDED kernels: true when the record says skip (block-uniform); otherwise the gradient scale times the clip coefficient
+template <bool GUARDED>
+__device__ __forceinline__ bool guard_skips(const float* __restrict__ guard, float& gscale) {
+    if (GUARDED) {
+        if (reinterpret_cast<const int*>(guard)[GUARD_SKIP] != 0) return true;
+        gscale *= guard[GUARD_COEF];
+    }
+    return false;
+}
 
 // the per-step scalars of one rule, computed in double from lr and the 1-based step, handed to the element loop as float
 struct StepScalars {
@@ -96,12 +114,14 @@ __device__ __forceinline__ void rule_one(float& p, float g, float& s0, float& s1
     }
 }
 
-template <int R>
+template <int R, bool GUARDED>
 __global__ void __launch_bounds__(256) flat_rule_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                          float* __restrict__ s0, float* __restrict__ s1, int64_t n,
                                                          const float* __restrict__ lr_dev, const int* __restrict__ step_dev,
                                                          double b1d, double b2d, float eps, float wd, float mu,
-                                                         float base_lr, float final_lr, float gamma, float gscale) {
+                                                         float base_lr, float final_lr, float gamma, float gscale,
+                                                         const float* __restrict__ guard) {
+    if (guard_skips<GUARDED>(guard, gscale)) return;
     const double t = (double)(step_dev[0] + 1);
     const StepScalars k = step_scalars<R>((double)lr_dev[0], t, b1d, b2d, wd, mu, base_lr, final_lr, gamma);
     // the betas and their complements rounded once from double (1 - 0.999f would be 1.3e-5 off 0.001)
@@ -127,7 +147,11 @@ __global__ void __launch_bounds__(256) flat_rule_kernel(float* __restrict__ p, c
         rule_one<R>(p[i], g[i], has0 ? s0[i] : z0, has1 ? s1[i] : z1, k, b1, b2, c1, c2, eps, wd, gscale);
 }
 
-__global__ void inc_step_kernel(int* p) { p[0] += 1; }
+template <bool GUARDED>
+__global__ void inc_step_kernel(int* p, const float* __restrict__ guard) {
+    if (GUARDED && reinterpret_cast<const int*>(guard)[GUARD_SKIP] != 0) return;     // a skipped step is not counted
+    p[0] += 1;
+}
 
 // ---- segmented rules --------------------------------------------------------------------------------------------
 // rows  [rows_total][3] int64: {first element, length, tensor}
@@ -161,12 +185,14 @@ __device__ __forceinline__ void adamp_row_one(float p, float g, float& m, float&
     acc[3] += (double)p * u;
 }
 
-template <int S>
+template <int S, bool GUARDED>
 __global__ void __launch_bounds__(256) seg_row_kernel(const int64_t* __restrict__ rows, int64_t rows_total,
                                                        const float* __restrict__ p, const float* __restrict__ g,
                                                        float* __restrict__ m, float* __restrict__ v,
                                                        float* __restrict__ partials, const int* __restrict__ step_dev,
-                                                       double b1, double b2, float eps, float gscale) {
+                                                       double b1, double b2, float eps, float gscale,
+                                                       const float* __restrict__ guard) {
+    if (guard_skips<GUARDED>(guard, gscale)) return;
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * SEG_WAVES + (threadIdx.x >> 6);
     if (row >= rows_total) return;
@@ -219,12 +245,13 @@ __device__ __forceinline__ double abs_cos(double pg, double gg, double pp, doubl
 
 // one wave per tensor.  AdamP: decision[t] (0 no projection, 1 channel view, 2 layer view) and aux[t] = {layer-view
 // coefficient sum(p*u) / (|p| + eps)^2, weight-decay ratio}.  NovoGrad: the blended gradient norm norm_avg[t].
-template <int S>
+template <int S, bool GUARDED>
 __global__ void __launch_bounds__(256) seg_fold_kernel(const int64_t* __restrict__ tens, int ntensors,
                                                         const float* __restrict__ partials, int* __restrict__ decision,
                                                         float* __restrict__ aux, float* __restrict__ norm_avg,
                                                         const int* __restrict__ step_dev, double b2, float eps, float delta,
-                                                        float wd_ratio) {
+                                                        float wd_ratio, const float* __restrict__ guard) {
+    if (GUARDED && reinterpret_cast<const int*>(guard)[GUARD_SKIP] != 0) return;
     const int lane = threadIdx.x & 63;
     const int tsr = blockIdx.x * SEG_WAVES + (threadIdx.x >> 6);
     if (tsr >= ntensors) return;                     // (wave-uniform: a wave owns one tensor)
@@ -282,7 +309,7 @@ __device__ __forceinline__ void novograd_apply_one(float& p, float g, float& m, 
     p = p - c.lr * ((mi * c.step_size) / den + c.wd * p);
 }
 
-template <int S>
+template <int S, bool GUARDED>
 __global__ void __launch_bounds__(256) seg_apply_kernel(const int64_t* __restrict__ rows, int64_t rows_total,
                                                          float* __restrict__ p, const float* __restrict__ g,
                                                          float* __restrict__ m, const float* __restrict__ v,
@@ -290,7 +317,9 @@ __global__ void __launch_bounds__(256) seg_apply_kernel(const int64_t* __restric
                                                          const int* __restrict__ decision, const float* __restrict__ aux,
                                                          const float* __restrict__ norm_avg,
                                                          const float* __restrict__ lr_dev, const int* __restrict__ step_dev,
-                                                         double b1, double b2, float eps, float wd, float gscale) {
+                                                         double b1, double b2, float eps, float wd, float gscale,
+                                                         const float* __restrict__ guard) {
+    if (guard_skips<GUARDED>(guard, gscale)) return;
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * SEG_WAVES + (threadIdx.x >> 6);
     if (row >= rows_total) return;
@@ -345,14 +374,105 @@ __global__ void __launch_bounds__(256) seg_apply_kernel(const int64_t* __restric
     }
 }
 
+// ---- gradient guard ---------------------------------------------------------------------------------------------
+constexpr int GUARD_MAX_BLOCKS = 1024;               // partials the one-block fold adds serially (4 blocks per CU)
+
+// blocks of the sum-of-squares pass: a function of n alone, so the summation order (and the result's bits) is too
+static inline int guard_blocks(int64_t n) { return (int)std::min<int64_t>(cdiv(cdiv(n, 4), 256), GUARD_MAX_BLOCKS); }
+
+__device__ __forceinline__ void sq_acc4(const float4 v, double (&acc)[4]) {
+    acc[0] = fma((double)v.x, (double)v.x, acc[0]);
+    acc[1] = fma((double)v.y, (double)v.y, acc[1]);
+    acc[2] = fma((double)v.z, (double)v.z, acc[2]);
+    acc[3] = fma((double)v.w, (double)v.w, acc[3]);
+}
+
+// partial[block] = sum of g[i]^2 over the block's grid-stride share, in double: a thread's elements in index order into four
+// accumulators (one per float4 component; the scalar tail into the first), those added pairwise, the wave butterfly, then
+// the block's four waves in wave order.  A finite float squared is at most 1.2e77: the sum cannot overflow, so a non-finite
+// sum means a non-finite element.
+__global__ void __launch_bounds__(256) grad_sumsq_kernel(const float* __restrict__ g, int64_t n, double* __restrict__ partial) {
+    __shared__ double wsum[4];
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    const int64_t n4 = (reinterpret_cast<uintptr_t>(g) & 15) ? 0 : n >> 2;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    for (; i + 3 * stride < n4; i += 4 * stride) {      // four 16-byte loads in flight per thread
+        const float4 a = reinterpret_cast<const float4*>(g)[i], b = reinterpret_cast<const float4*>(g)[i + stride];
+        const float4 c = reinterpret_cast<const float4*>(g)[i + 2 * stride], d = reinterpret_cast<const float4*>(g)[i + 3 * stride];
+        sq_acc4(a, acc);
+        sq_acc4(b, acc);
+        sq_acc4(c, acc);
+        sq_acc4(d, acc);
+    }
+    for (; i < n4; i += stride) sq_acc4(reinterpret_cast<const float4*>(g)[i], acc);
+    for (int64_t j = n4 * 4 + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; j < n; j += stride)
+        acc[0] = fma((double)g[j], (double)g[j], acc[0]);
+    const double v = wave_sum((acc[0] + acc[1]) + (acc[2] + acc[3]));
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) partial[blockIdx.x] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+}
+
+// one block: the partials added in index order, then the record.  torch.nn.utils.clip_grad_norm_'s arithmetic in double,
+// stored as float: coef = min(max_norm / (norm + 1e-6), 1) - a NaN stays a NaN, as torch.clamp keeps it.
+__global__ void __launch_bounds__(256) grad_guard_fold_kernel(const double* __restrict__ partial, int blocks, double grad_scale,
+                                                              double max_norm, int skip_nonfinite, float* __restrict__ guard) {
+    __shared__ double sh[GUARD_MAX_BLOCKS];
+    for (int i = threadIdx.x; i < blocks; i += 256) sh[i] = partial[i];
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    double sum = 0.0;
+    for (int i = 0; i < blocks; ++i) sum += sh[i];
+    const double norm = grad_scale * sqrt(sum);
+    const float norm_f = (float)norm;
+    const bool finite = isfinite(norm);              // (of the double: finite elements whose norm exceeds fp32 still clip)
+    double coef = 1.0;
+    if (max_norm > 0.0) {
+        coef = max_norm / (norm + 1e-6);
+        if (coef > 1.0) coef = 1.0;
+    }
+    const bool skip = skip_nonfinite != 0 && !finite;
+    int* gi = reinterpret_cast<int*>(guard);
+    int64_t* gl = reinterpret_cast<int64_t*>(guard);
+    guard[GUARD_NORM] = norm_f;
+    guard[GUARD_COEF] = (float)coef;
+    gi[GUARD_SKIP] = skip ? 1 : 0;
+    gi[GUARD_SKIPPED_ROW] = skip ? gi[GUARD_SKIPPED_ROW] + 1 : 0;
+    gl[GUARD_STEPS64] += 1;
+    if (!skip && coef < 1.0) gl[GUARD_STEPS64 + 1] += 1;
+    if (skip) gl[GUARD_STEPS64 + 2] += 1;
+    if (isfinite(norm_f) && norm_f > guard[GUARD_NORM_MAX]) guard[GUARD_NORM_MAX] = norm_f;
+}
+
 }  // namespace xv2
 
 using namespace xv2;
+
+extern "C" size_t xv2_grad_guard_workspace(int64_t n) { return n > 0 ? (size_t)guard_blocks(n) * sizeof(double) : 0; }
+
+extern "C" int xv2_grad_guard(const float* grad, int64_t n, float grad_scale, float max_norm, int skip_nonfinite,
+                              void* workspace, void* guard, void* stream) {
+    XV2_CHECK_ARG(grad && guard, "grad_guard: null gradient buffer or guard record");
+    XV2_CHECK_ARG(n > 0, "grad_guard: n = %lld, must be positive", (long long)n);
+    XV2_CHECK_ARG(std::isfinite(max_norm) && max_norm >= 0.f, "grad_guard: max_norm = %g, must be finite and >= 0 (0: no clipping)",
+                  (double)max_norm);
+    XV2_CHECK_ARG(workspace, "grad_guard: a guard needs its workspace (xv2_grad_guard_workspace bytes)");
+    hipStream_t s = (hipStream_t)stream;
+    const int blocks = guard_blocks(n);
+    hipLaunchKernelGGL(grad_sumsq_kernel, dim3(blocks), dim3(256), 0, s, grad, n, static_cast<double*>(workspace));
+    XV2_CHECK_LAUNCH();
+    hipLaunchKernelGGL(grad_guard_fold_kernel, dim3(1), dim3(256), 0, s, static_cast<const double*>(workspace), blocks,
+                       (double)grad_scale, (double)max_norm, skip_nonfinite, static_cast<float*>(guard));
+    XV2_CHECK_LAUNCH();
+    return XV2_OK;
+}
 
 extern "C" int xv2_flat_step_dev(int rule, float* param, const float* grad, float* state0, float* state1, int64_t n,
                                  const float* lr_dev, int* step_dev, double beta1, double beta2, float eps,
                                  float weight_decay, float momentum, float base_lr, float final_lr, float gamma,
                                  float grad_scale, void* stream) {
+    OptimGuardScope scope;          // (the guard named for this call, cleared on every way out)
     XV2_CHECK_ARG(param && grad && lr_dev && step_dev && n > 0, "flat_step_dev: null buffer or empty");
     XV2_CHECK_ARG(rule >= RULE_SGD && rule <= RULE_ADABOUND, "flat_step_dev: unknown rule %d", rule);
     XV2_CHECK_ARG(rule == RULE_SGD || state0, "flat_step_dev: rule %d keeps a first state buffer", rule);
@@ -360,9 +480,17 @@ extern "C" int xv2_flat_step_dev(int rule, float* param, const float* grad, floa
     XV2_CHECK_ARG(rule != RULE_ADABOUND || base_lr > 0.f, "flat_step_dev: adabound needs base_lr > 0");
     const int grid = (int)std::min<int64_t>(cdiv(cdiv(n, 4), 256), 4096);
     hipStream_t s = (hipStream_t)stream;
-#define XV2_RULE_LAUNCH(R)                                                                                             \
-    hipLaunchKernelGGL(flat_rule_kernel<R>, dim3(grid), dim3(256), 0, s, param, grad, state0, state1, n, lr_dev,     \
-                       step_dev, beta1, beta2, eps, weight_decay, momentum, base_lr, final_lr, gamma, grad_scale)
+    const float* guard = scope.guard;
+#define XV2_RULE_LAUNCH_G(R, G)                                                                                        \
+    hipLaunchKernelGGL((flat_rule_kernel<R, G>), dim3(grid), dim3(256), 0, s, param, grad, state0, state1, n, lr_dev, \
+                       step_dev, beta1, beta2, eps, weight_decay, momentum, base_lr, final_lr, gamma, grad_scale, guard)
+#define XV2_RULE_LAUNCH(R)                   \
+    do {                                     \
+        if (guard)                           \
+            XV2_RULE_LAUNCH_G(R, true);      \
+        else                                 \
+            XV2_RULE_LAUNCH_G(R, false);     \
+    } while (0)
     switch (rule) {
         case RULE_SGD: XV2_RULE_LAUNCH(RULE_SGD); break;
         case RULE_SGD_MOMENTUM: XV2_RULE_LAUNCH(RULE_SGD_MOMENTUM); break;
@@ -371,8 +499,33 @@ extern "C" int xv2_flat_step_dev(int rule, float* param, const float* grad, floa
         default: XV2_RULE_LAUNCH(RULE_ADABOUND);
     }
 #undef XV2_RULE_LAUNCH
+#undef XV2_RULE_LAUNCH_G
     XV2_CHECK_LAUNCH();
-    hipLaunchKernelGGL(inc_step_kernel, dim3(1), dim3(1), 0, s, step_dev);
+    if (guard)
+        hipLaunchKernelGGL(inc_step_kernel<true>, dim3(1), dim3(1), 0, s, step_dev, guard);
+    else
+        hipLaunchKernelGGL(inc_step_kernel<false>, dim3(1), dim3(1), 0, s, step_dev, guard);
+    XV2_CHECK_LAUNCH();
+    return XV2_OK;
+}
+
+template <bool G>
+static int adamp_launch(const int64_t* rows, int64_t rows_total, const int64_t* tensors, int ntensors, float* param,
+                        const float* grad, float* exp_avg, float* exp_avg_sq, float* partials, int* decision, float* aux,
+                        const float* lr_dev, int* step_dev, double beta1, double beta2, float eps, float weight_decay,
+                        float delta, float wd_ratio, float grad_scale, const float* guard, hipStream_t s) {
+    const unsigned rgrid = (unsigned)cdiv(rows_total, SEG_WAVES), tgrid = (unsigned)cdiv(ntensors, SEG_WAVES);
+    hipLaunchKernelGGL((seg_row_kernel<SEG_ADAMP, G>), dim3(rgrid), dim3(256), 0, s, rows, rows_total, param, grad, exp_avg,
+                       exp_avg_sq, partials, step_dev, beta1, beta2, eps, grad_scale, guard);
+    XV2_CHECK_LAUNCH();
+    hipLaunchKernelGGL((seg_fold_kernel<SEG_ADAMP, G>), dim3(tgrid), dim3(256), 0, s, tensors, ntensors, partials, decision, aux,
+                       (float*)nullptr, step_dev, beta2, eps, delta, wd_ratio, guard);
+    XV2_CHECK_LAUNCH();
+    hipLaunchKernelGGL((seg_apply_kernel<SEG_ADAMP, G>), dim3(rgrid), dim3(256), 0, s, rows, rows_total, param, grad, exp_avg,
+                       exp_avg_sq, partials, decision, aux, (const float*)nullptr, lr_dev, step_dev, beta1, beta2, eps,
+                       weight_decay, grad_scale, guard);
+    XV2_CHECK_LAUNCH();
+    hipLaunchKernelGGL(inc_step_kernel<G>, dim3(1), dim3(1), 0, s, step_dev, guard);
     XV2_CHECK_LAUNCH();
     return XV2_OK;
 }
@@ -382,21 +535,35 @@ extern "C" int xv2_adamp_step_dev(const int64_t* rows, int64_t rows_total, const
                                   int* decision, float* aux, const float* lr_dev, int* step_dev, double beta1, double beta2,
                                   float eps, float weight_decay, float delta, float wd_ratio, float grad_scale,
                                   void* stream) {
+    OptimGuardScope scope;
     XV2_CHECK_ARG(rows && tensors && param && grad && exp_avg && exp_avg_sq && partials && decision && aux && lr_dev &&
                   step_dev && rows_total > 0 && ntensors > 0, "adamp_step_dev: null buffer or empty table");
-    hipStream_t s = (hipStream_t)stream;
+    return scope.guard
+               ? adamp_launch<true>(rows, rows_total, tensors, ntensors, param, grad, exp_avg, exp_avg_sq, partials, decision,
+                                    aux, lr_dev, step_dev, beta1, beta2, eps, weight_decay, delta, wd_ratio, grad_scale,
+                                    scope.guard, (hipStream_t)stream)
+               : adamp_launch<false>(rows, rows_total, tensors, ntensors, param, grad, exp_avg, exp_avg_sq, partials, decision,
+                                     aux, lr_dev, step_dev, beta1, beta2, eps, weight_decay, delta, wd_ratio, grad_scale,
+                                     nullptr, (hipStream_t)stream);
+}
+
+template <bool G>
+static int novograd_launch(const int64_t* rows, int64_t rows_total, const int64_t* tensors, int ntensors, float* param,
+                           const float* grad, float* exp_avg, float* norm_avg, float* partials, const float* lr_dev,
+                           int* step_dev, double beta1, double beta2, float eps, float weight_decay, float grad_scale,
+                           const float* guard, hipStream_t s) {
     const unsigned rgrid = (unsigned)cdiv(rows_total, SEG_WAVES), tgrid = (unsigned)cdiv(ntensors, SEG_WAVES);
-    hipLaunchKernelGGL(seg_row_kernel<SEG_ADAMP>, dim3(rgrid), dim3(256), 0, s, rows, rows_total, param, grad, exp_avg,
-                       exp_avg_sq, partials, step_dev, beta1, beta2, eps, grad_scale);
+    hipLaunchKernelGGL((seg_row_kernel<SEG_NOVOGRAD, G>), dim3(rgrid), dim3(256), 0, s, rows, rows_total, param, grad,
+                       (float*)nullptr, (float*)nullptr, partials, step_dev, beta1, beta2, eps, grad_scale, guard);
     XV2_CHECK_LAUNCH();
-    hipLaunchKernelGGL(seg_fold_kernel<SEG_ADAMP>, dim3(tgrid), dim3(256), 0, s, tensors, ntensors, partials, decision, aux,
-                       (float*)nullptr, step_dev, beta2, eps, delta, wd_ratio);
+    hipLaunchKernelGGL((seg_fold_kernel<SEG_NOVOGRAD, G>), dim3(tgrid), dim3(256), 0, s, tensors, ntensors, partials,
+                       (int*)nullptr, (float*)nullptr, norm_avg, step_dev, beta2, eps, 0.f, 1.f, guard);
     XV2_CHECK_LAUNCH();
-    hipLaunchKernelGGL(seg_apply_kernel<SEG_ADAMP>, dim3(rgrid), dim3(256), 0, s, rows, rows_total, param, grad, exp_avg,
-                       exp_avg_sq, partials, decision, aux, (const float*)nullptr, lr_dev, step_dev, beta1, beta2, eps,
-                       weight_decay, grad_scale);
+    hipLaunchKernelGGL((seg_apply_kernel<SEG_NOVOGRAD, G>), dim3(rgrid), dim3(256), 0, s, rows, rows_total, param, grad,
+                       exp_avg, (const float*)nullptr, partials, (const int*)nullptr, (const float*)nullptr, norm_avg,
+                       lr_dev, step_dev, beta1, beta2, eps, weight_decay, grad_scale, guard);
     XV2_CHECK_LAUNCH();
-    hipLaunchKernelGGL(inc_step_kernel, dim3(1), dim3(1), 0, s, step_dev);
+    hipLaunchKernelGGL(inc_step_kernel<G>, dim3(1), dim3(1), 0, s, step_dev, guard);
     XV2_CHECK_LAUNCH();
     return XV2_OK;
 }
@@ -405,21 +572,13 @@ extern "C" int xv2_novograd_step_dev(const int64_t* rows, int64_t rows_total, co
                                      float* param, const float* grad, float* exp_avg, float* norm_avg, float* partials,
                                      const float* lr_dev, int* step_dev, double beta1, double beta2, float eps,
                                      float weight_decay, float grad_scale, void* stream) {
+    OptimGuardScope scope;
     XV2_CHECK_ARG(rows && tensors && param && grad && exp_avg && norm_avg && partials && lr_dev && step_dev &&
                   rows_total > 0 && ntensors > 0, "novograd_step_dev: null buffer or empty table");
-    hipStream_t s = (hipStream_t)stream;
-    const unsigned rgrid = (unsigned)cdiv(rows_total, SEG_WAVES), tgrid = (unsigned)cdiv(ntensors, SEG_WAVES);
-    hipLaunchKernelGGL(seg_row_kernel<SEG_NOVOGRAD>, dim3(rgrid), dim3(256), 0, s, rows, rows_total, param, grad,
-                       (float*)nullptr, (float*)nullptr, partials, step_dev, beta1, beta2, eps, grad_scale);
-    XV2_CHECK_LAUNCH();
-    hipLaunchKernelGGL(seg_fold_kernel<SEG_NOVOGRAD>, dim3(tgrid), dim3(256), 0, s, tensors, ntensors, partials,
-                       (int*)nullptr, (float*)nullptr, norm_avg, step_dev, beta2, eps, 0.f, 1.f);
-    XV2_CHECK_LAUNCH();
-    hipLaunchKernelGGL(seg_apply_kernel<SEG_NOVOGRAD>, dim3(rgrid), dim3(256), 0, s, rows, rows_total, param, grad,
-                       exp_avg, (const float*)nullptr, partials, (const int*)nullptr, (const float*)nullptr, norm_avg,
-                       lr_dev, step_dev, beta1, beta2, eps, weight_decay, grad_scale);
-    XV2_CHECK_LAUNCH();
-    hipLaunchKernelGGL(inc_step_kernel, dim3(1), dim3(1), 0, s, step_dev);
-    XV2_CHECK_LAUNCH();
-    return XV2_OK;
+    return scope.guard ? novograd_launch<true>(rows, rows_total, tensors, ntensors, param, grad, exp_avg, norm_avg, partials,
+                                               lr_dev, step_dev, beta1, beta2, eps, weight_decay, grad_scale, scope.guard,
+                                               (hipStream_t)stream)
+                       : novograd_launch<false>(rows, rows_total, tensors, ntensors, param, grad, exp_avg, norm_avg, partials,
+                                                lr_dev, step_dev, beta1, beta2, eps, weight_decay, grad_scale, nullptr,
+                                                (hipStream_t)stream);
 }

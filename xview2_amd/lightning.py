@@ -190,8 +190,9 @@ class Model(_Base):
         f1, per_class = self._finish_epoch()
         if f1 >= self.best_f1:
             self.best_f1, self.best_epoch = f1, self.current_epoch
-        self._report(self.current_epoch, {"f1": round(f1.item(), 3), "val_loss": round(val_loss.item(), 3),
-                                          "top_f1": round(self.best_f1.item(), 3)}, per_class)
+        metrics = {"f1": round(f1.item(), 3), "val_loss": round(val_loss.item(), 3), "top_f1": round(self.best_f1.item(), 3)}
+        metrics.update(getattr(self, "epoch_extras", None) or {})      # the trainer's gradient-guard counters, when set
+        self._report(self.current_epoch, metrics, per_class)
         self.log("f1_score", f1.cpu())
         self.log("val_loss", val_loss.cpu())
 

@@ -55,6 +55,45 @@ class FlatOptimizer:
         self.lr_dev = torch.tensor([lr], dtype=torch.float32, device=dev) if dev.type == "cuda" else None
         self.step_dev = torch.zeros(1, dtype=torch.int32, device=dev) if dev.type == "cuda" else None
         self._lr_on_dev = lr
+        self.guard = None                  # the gradient guard's device record (set_guard)
+
+    # ------------------------------------------------------------------ gradient guard
+    def set_guard(self, max_norm=0.0, skip_nonfinite=False):
+        """clip the global gradient norm to `max_norm` (0: no clipping; torch.nn.utils.clip_grad_norm_'s arithmetic) and /
+        or skip a step whose gradient holds an Inf or NaN: two launches over flat_g in front of the rule (include/xv2.h
+        xv2_grad_guard), decided and applied on the device - nothing syncs, and a captured step keeps it.  The record and
+        the workspace are allocated once; a later call changes the settings and keeps the counters."""
+        max_norm = float(max_norm)
+        if not (0.0 <= max_norm < float("inf")):
+            raise ValueError("max_norm = %r: must be finite and >= 0 (0: no clipping)" % max_norm)
+        if not self.capturable:
+            raise RuntimeError("the gradient guard runs on the GPU only (HIP kernels; there is no CPU fallback)")
+        if self.guard is None:
+            from ._capi import query
+            dev = self.flat_g.device
+            self.guard = torch.zeros(8, dtype=torch.int64, device=dev)           # 64 bytes, layout in include/xv2.h
+            self._guard_ws = torch.zeros(query("xv2_grad_guard_workspace", self.total) // 8, dtype=torch.float64, device=dev)
+        self._guard_cfg = (max_norm, int(bool(skip_nonfinite)))
+
+    def _guard_pass(self, grad_scale):
+        """the norm pass over the (reduced, gathered) gradient, then the record named for the rule's entry point: call
+        right before _launch"""
+        if self.guard is None:
+            return
+        from ._capi import _func, call
+        call("xv2_grad_guard", self.flat_g, self.total, float(grad_scale), self._guard_cfg[0], self._guard_cfg[1],
+             self._guard_ws, self.guard)
+        _func("xv2_optim_guard_ctx")(self.guard.data_ptr())
+
+    def guard_stats(self):
+        """the guard's record as a dict (the last step's norm / coef / skip, the cumulative counters, the largest finite
+        norm).  Reading it synchronises with the device: the caller chooses when."""
+        if self.guard is None:
+            raise RuntimeError("no gradient guard is set (set_guard)")
+        rec = self.guard.cpu()
+        f, i = rec.view(torch.float32), rec.view(torch.int32)
+        return {"norm": float(f[0]), "coef": float(f[1]), "skip": int(i[2]), "skipped_in_a_row": int(i[3]),
+                "steps": int(rec[2]), "clipped": int(rec[3]), "skipped": int(rec[4]), "norm_max": float(f[10])}
 
     def zero_grad(self):
         ops.begin_step()               # (a backward pass that raised leaves its side-stream bookkeeping behind)
@@ -87,6 +126,7 @@ class FlatOptimizer:
         if not self.capturable:
             raise RuntimeError("%s steps on the GPU only (HIP kernels; there is no CPU fallback)" % type(self).__name__)
         self.sync_lr()
+        self._guard_pass(grad_scale)
         self._launch(float(grad_scale))
         ops.weights_changed()
         ops.repack_all()       # the packed conv-weight layouts, refreshed in one launch
@@ -102,7 +142,9 @@ class FlatOptimizer:
         pass
 
     def state_dict(self):
-        sd = {"step": self.step_count}
+        # under a guard the device counter is the truth: the host's count runs ahead after a skipped step, and a resumed
+        # run must continue the bias corrections where the device stands (this read synchronises)
+        sd = {"step": self.step_count if self.guard is None else int(self.step_dev.item())}
         sd.update((name, getattr(self, name)) for name in self.STATE)
         sd.update(self._extra_state())
         sd["lr"] = self.param_groups[0]["lr"]
@@ -137,6 +179,7 @@ class FlatAdamW(FlatOptimizer):
         if self.capturable:
             from ._capi import call
             self.sync_lr()
+            self._guard_pass(grad_scale)
             call("xv2_adamw_step_dev", self.flat_p, self.flat_g, self.exp_avg, self.exp_avg_sq, self.flat_p.numel(),
                  self.lr_dev, float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.weight_decay),
                  self.step_dev, float(grad_scale))

@@ -17,8 +17,13 @@ from .optim import FlatOptimizer
 class Trainer:
     def __init__(self, gpus=1, precision=32, max_epochs=1, min_epochs=None, sync_batchnorm=False, accelerator=None,
                  default_root_dir=".", resume_from_checkpoint=None, checkpoint_callback=True, callbacks=None,
-                 benchmark=True, deterministic=False, num_sanity_val_steps=0, logger=False, log_every=0):
+                 benchmark=True, deterministic=False, num_sanity_val_steps=0, logger=False, log_every=0,
+                 gradient_clip_val=0.0, skip_nonfinite=False):
         self.gpus, self.max_epochs, self.root = gpus, max_epochs, default_root_dir
+        # PL's gradient_clip_val (global-norm clipping, 0 = off) and the step skipping of its native-AMP GradScaler: the flat
+        # optimizer's gradient guard (optim.FlatOptimizer.set_guard).  guard_log: one dict per epoch when a guard is set.
+        self.gradient_clip_val, self.skip_nonfinite = float(gradient_clip_val), bool(skip_nonfinite)
+        self.guard_log = []
         self.sync_batchnorm, self.resume = sync_batchnorm, resume_from_checkpoint
         self.checkpointing = bool(checkpoint_callback)
         self.log_every = log_every
@@ -74,6 +79,12 @@ class Trainer:
                 if isinstance(optimizer, FlatOptimizer):
                     optimizer.sync_lr()
         flat = isinstance(optimizer, FlatOptimizer)
+        guarded = self.gradient_clip_val > 0.0 or self.skip_nonfinite
+        if guarded:
+            if not flat:
+                raise RuntimeError("gradient_clip_val / skip_nonfinite need a flat optimizer (xview2_amd.optim)")
+            optimizer.set_guard(self.gradient_clip_val, self.skip_nonfinite)
+        seen = {"steps": 0, "clipped": 0, "skipped": 0}
         reducer = xdist.GradReducer(optimizer, sync_bn=self.sync_batchnorm or self.world > 1) if flat else None
         frozen = False
         for epoch in range(start_epoch, self.max_epochs):
@@ -104,7 +115,11 @@ class Trainer:
                 if self.log_every and self.rank == 0 and self.global_step % self.log_every == 0:
                     print("epoch %d step %d loss %.5f" % (epoch, self.global_step, float(loss)))
             xdist.check_peer_exchange()          # one-shot SyncBatchNorm exchange: a timed-out exchange is an error, per epoch
+            if guarded:
+                self._report_guard(model, optimizer, epoch, seen)
             score = self.validate(model, datamodule)
+            if guarded:
+                model.epoch_extras = None
             if self.checkpointing:
                 ckdir = os.path.join(self.root, "checkpoints")
                 self.save_checkpoint(model, os.path.join(ckdir, "last.ckpt"), epoch, optimizer)
@@ -121,6 +136,23 @@ class Trainer:
         if frozen:
             gc.unfreeze()
         return model
+
+    def _report_guard(self, model, optimizer, epoch, seen):
+        """end of an epoch, where validation synchronises anyway: this epoch's share of the guard's counters, handed to the
+        model for the epoch's record (lightning.Model.validation_epoch_end).  Every rank took the same decisions on the same
+        reduced gradient, so every rank raises together when the epoch trained nothing."""
+        st = optimizer.guard_stats()
+        steps, clipped, skipped = (st[k] - seen[k] for k in ("steps", "clipped", "skipped"))
+        seen.update((k, st[k]) for k in seen)
+        rec = {"grad_norm_max": st["norm_max"], "clipped_steps": clipped, "skipped_steps": skipped}
+        self.guard_log.append(dict(rec, epoch=epoch, steps=steps, total=st))
+        model.epoch_extras = rec
+        if self.rank == 0:
+            print("epoch %d gradient guard: largest norm %.6g, %d of %d steps clipped, %d skipped (non-finite gradient)"
+                  % (epoch, st["norm_max"], clipped, steps, skipped))
+        if steps > 0 and skipped == steps:
+            raise RuntimeError("every step of epoch %d was skipped for a non-finite gradient (%d of %d): training is dead"
+                               % (epoch, skipped, steps))
 
     @torch.no_grad()
     def validate(self, model, datamodule):
