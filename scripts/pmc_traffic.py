@@ -23,8 +23,11 @@ def per_kernel(db, counter):
 
 def pretty(mangled):
     """mangled kernel symbol -> the name bench.py's in-library profiler registers (roofline.kernel)"""
-    if "wgrad_alltaps_x3_kernel" in mangled or "wgrad_alltaps64_x3_kernel" in mangled:      # (one registered name for both tilings)
-        return "wgrad_alltaps_kernel<f16x2>" if "ILi2E" in mangled else "wgrad_alltaps_kernel<f32x3>"
+    m = re.match(r"_ZN3xv2\d+wgrad_alltaps(64)?_x3_kernelILi(\d)E", mangled)
+    if m:
+        return "wgrad_alltaps%s_kernel<%s>" % (m.group(1) or "", "f16x2" if m.group(2) == "2" else "f32x3")
+    if "wgrad_alltaps64_tr_kernel" in mangled:
+        return "wgrad_alltaps64_kernel<bf16hbm>"
     m = re.match(r"_ZN3xv2\d+wgrad_tr_x3_kernelILi(\d+)ELi(\d+)ELi(\d)E", mangled)
     if m:
         return "wgrad_tr_kernel<%s,%s,%s>" % (m.group(1), m.group(2), "f16x2" if m.group(3) == "2" else "f32x3")
@@ -56,14 +59,13 @@ def pretty(mangled):
         tag = ("rgb", "rgb,bf16out", "c32", "c32,bf16", "c32,bf16hbm", "c32,bf16hbm,halo", "c32,f32x3", "c32,f32x3,halo",
                "c32,f32x3,halo,wx3", "c32,f16x2", "c32,f16x2,halo,wx2")[form]
         return "igemm_kernel<%d,%d,%d,%d,%s>" % (bm, bn, 4 if bn == 32 else 2, 1 if bn == 32 else 2, tag)
-    m = re.match(r"_ZN3xv2\d+wgrad_kernelI(.*?)EEv", mangled)
+    m = re.match(r"_ZN3xv2\d+wgrad_kernelILNS_5WFormE(\d+)ELi(\d+)ELi(\d+)EEEv", mangled)
     if not m:
-        return None
-    args = re.findall(r"L([ib])(\d+)E", m.group(1))
-    vals = [int(v) for _, v in args] + [0, 0, 0, 0, 0, 0, 0]
-    smallc, bf16, hs = vals[5], vals[6], vals[7]
-    tag = ("rgb" if smallc else ("c32,bf16" if bf16 else "c32")) + (",bf16hbm" if hs else "")
-    return "wgrad_kernel<%d,%d,%d,%d,%d,%s>" % (vals[0], vals[1], vals[2], vals[3], vals[4], tag)
+        return None      # enum WForm of wgrad_kernel.h, in its order; waves of a block (co x ci x pixels) from the tile as tile_wgm / tile_wk there
+    form, bm, bn = (int(v) for v in m.groups())
+    tag = ("rgb", "rgb,bf16hbm", "c32", "c32,bf16", "c32,bf16,bf16hbm", "c32,bf16hbm")[form]
+    wgm, wgn = min(bm // 32, 2), min(bn // 32, 2)
+    return "wgrad_kernel<%d,%d,%d,%d,%d,%s>" % (bm, bn, wgm, wgn, 4 // (wgm * wgn), tag)
 
 
 f, nf = per_kernel(sys.argv[1], "FETCH_SIZE")

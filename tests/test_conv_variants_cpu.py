@@ -1,7 +1,8 @@
 """CPU side of the convolution variant matrix (tests/test_conv_variants_gpu.py) and of its gates (tests/conv_ref.py):
 - the gates have teeth: torch's fp32 convolution passes both, and each of three plausible kernel faults fails one;
-- the variant table is complete: it lists exactly the kernel instantiations of the convolution sources, under the names the
-  library registers, and the cases name every entry that is not ablation-only."""
+- the variant table is complete: it lists exactly the kernel instantiations of the convolution sources (the rows of the
+  weight-gradient kernel table among them), under the names the library registers, and the cases name every entry that is not
+  ablation-only."""
 import math
 import os
 import re
@@ -147,14 +148,30 @@ def expand_launch_macros(t):
     return t
 
 
+def _top_level_args(s):
+    """s split at the commas outside ( ) and < >"""
+    out, depth, cur = [], 0, ""
+    for ch in s:
+        depth += ch in "(<"
+        depth -= ch in ")>"
+        if ch == "," and depth == 0:
+            out.append(cur.strip())
+            cur = ""
+        else:
+            cur += ch
+    return out + [cur.strip()]
+
+
 def source_variants(texts):
     """keys of VARIANTS found in the given source texts -> the profiler name each registers (None: derived from the template
     arguments, registered_name())"""
     keys = {}
     for t in texts:
         t = expand_launch_macros(t)
-        for m in re.finditer(r"\b(launch_one|launch_wgrad|sg_launch_one)<([^<>]*)>\s*\(", t):
+        for m in re.finditer(r"\b(launch_one|sg_launch_one)<([^<>]*)>\s*\(", t):
             keys["%s<%s>" % (m.group(1), ",".join(a.strip() for a in m.group(2).split(",")))] = None
+        for m in re.finditer(r'^\s*XV2_WGRAD_ROW\(\s*"([^"]*)"\s*,(.*)\)\s*$', t, flags=re.M):      # (NAME, ..., kernel): a table row
+            keys["XV2_WGRAD_ROW(%s)" % _top_level_args(m.group(2))[-1].replace(" ", "")] = m.group(1)
         for m in re.finditer(r'\bthin_launch_one<([^<>]*)>\s*\(\s*q\s*,\s*"([^"]*)"', t):
             keys["thin_launch_one<%s>" % ",".join(a.strip() for a in m.group(1).split(","))] = m.group(2)
         for m in re.finditer(r'\bprof_register\("([^"]*)"\)', t):
@@ -168,27 +185,22 @@ def _texts():
 
 def registered_name(key):
     """the profiler name the library registers for a VARIANTS key whose name is built from its template arguments
-    (restating launch_one / launch_wgrad / sg_launch_one of igemm_conv.hip / wgrad_conv.hip / sg_conv.hip)"""
-    m = re.match(r"(launch_one|launch_wgrad|sg_launch_one)<(.*)>$", key)
+    (restating launch_one / sg_launch_one of igemm_conv.hip / sg_conv.hip)"""
+    m = re.match(r"(launch_one|sg_launch_one)<(.*)>$", key)
     a = m.group(2).split(",")
     t = lambda i, dflt: (a[i] == "true") if i < len(a) else dflt
     if m.group(1) == "launch_one":
         form, BM, BN = a
         WGM, WGN = ("4", "1") if BN == "32" else ("2", "2")      # waves of a block along M x N: a function of the tile
         return "igemm_kernel<%s,%s,%s,%s,%s>" % (BM, BN, WGM, WGN, _IGEMM_FORMS[form[len("Form::"):]])
-    if m.group(1) == "sg_launch_one":
-        WM, G, NB = (int(v) for v in a[:3])
-        return "sg_conv_kernel<%d,%d,g%d,%s%s>" % (32 * WM, 32 * NB, G, "1x1," if t(3, False) else "", "bf16hbm" if t(4, False) else "f16x2")
-    BM, BN, WGM, WGN, WK = a[:5]
-    SMALLC, BF16, HS = t(5, False), t(6, False), t(7, False)
-    return "wgrad_kernel<%s,%s,%s,%s,%s,%s%s>" % (BM, BN, WGM, WGN, WK, "rgb" if SMALLC else ("c32,bf16" if BF16 else "c32"),
-                                                  ",bf16hbm" if HS else "")
+    WM, G, NB = (int(v) for v in a[:3])
+    return "sg_conv_kernel<%d,%d,g%d,%s%s>" % (32 * WM, 32 * NB, G, "1x1," if t(3, False) else "", "bf16hbm" if t(4, False) else "f16x2")
 
 
 def test_variant_table_lists_exactly_the_instantiations_of_the_conv_sources():
     from tests.test_conv_variants_gpu import VARIANTS
     src = set(source_variants(_texts()))
-    assert len(src) >= 115
+    assert len(src) >= 118
     assert set(VARIANTS) == src, ("in the sources, not in VARIANTS: %s" % sorted(src - set(VARIANTS)),
                                   "in VARIANTS, not in the sources: %s" % sorted(set(VARIANTS) - src))
 
@@ -199,8 +211,10 @@ def test_an_added_instantiation_is_caught():
     texts[0] += "\n    return launch_one<Form::F32X3, 64, 32>(p, stream);\n"
     texts[3] = texts[3].replace("    XV2_THIN_CASE(64, 64)\n", "    XV2_THIN_CASE(64, 64)\n    XV2_THIN_CASE(32, 64)\n")
     texts[2] = texts[2].replace("        XV2_SG_CASE(242, 2, 4, 2)\n", "        XV2_SG_CASE(242, 2, 4, 2)\n        XV2_SG_CASE(222, 2, 2, 2)\n")
+    texts[1] = texts[1].replace("#undef XV2_WGRAD_ROW\n", '    XV2_WGRAD_ROW("wgrad_kernel<64,32,2,1,2,c32,bf16hbm>", C32_BF16HBM, 64, 32, '
+                                "tiled_lds(64, 32), 2, 2, X_IN, wgrad_kernel<WForm::C32_BF16HBM, 64, 32>)\n#undef XV2_WGRAD_ROW\n")
     added = set(source_variants(texts)) - set(VARIANTS)
-    assert added == {"launch_one<Form::F32X3,64,32>", "thin_launch_one<32,64,true,2,2>",
+    assert added == {"launch_one<Form::F32X3,64,32>", "XV2_WGRAD_ROW(wgrad_kernel<WForm::C32_BF16HBM,64,32>)", "thin_launch_one<32,64,true,2,2>",
                      "thin_launch_one<32,64,true,2,4>", "thin_launch_one<32,64,false,4,4,0,2>", "thin_launch_one<32,64,false,4,4>",
                      "sg_launch_one<2,2,2,true,true>", "sg_launch_one<2,2,2,false,true>", "sg_launch_one<2,2,2,true,false>",
                      "sg_launch_one<2,2,2,false,false>"}, sorted(added)

@@ -1,12 +1,11 @@
 """Every convolution kernel variant against a float64 reference, at the shapes, math modes and edges where kernels go wrong.
 
 VARIANTS names the kernel instantiations of the convolution sources that carry a profiler name of their own - each distinct
-launch_one<...> / launch_wgrad<...> / sg_launch_one<...> / thin_launch_one<...> template argument list (the XV2_IGEMM_TILES,
-XV2_SG_CASE and XV2_THIN_CASE macros expanded) and each prof_register("...") literal - with that name.  An instantiation that only an A/B
-switch reaches reads "ablation-only: XV2_<switch>".  tests/test_conv_variants_cpu.py keeps the table equal to the sources and
-checks that the cases below reach every other entry.  Not told apart: the device kernels launched under one prof_register
-name - the all-taps weight gradient's 64 x 64 and 32 x 32 tile forms (wgrad_alltaps64_* / wgrad_alltaps_*) and its three
-bf16-storage forms, the tile forms of the transpose-read kernel - count as that one name.
+launch_one<...> / sg_launch_one<...> / thin_launch_one<...> template argument list (the XV2_IGEMM_TILES, XV2_SG_CASE and
+XV2_THIN_CASE macros expanded), each XV2_WGRAD_ROW(...) row of the weight-gradient kernel table (keyed by its kernel) and each
+prof_register("...") literal - with that name.  An instantiation that only an A/B switch reaches reads
+"ablation-only: XV2_<switch>".  tests/test_conv_variants_cpu.py keeps the table equal to the sources and checks that the cases
+below reach every other entry.
 
 A case calls the C ABI directly (xview2_amd._capi.call with an ops._desc descriptor, weights packed by xv2_pack_weight) and
 asserts the exact profiler names of its launches (EXPECT).  Every output, workspace, statistics buffer, packed weight operand
@@ -76,26 +75,40 @@ VARIANTS = {
     "launch_one<Form::C32,128,64>": "igemm_kernel<128,64,2,2,c32>",
     "launch_one<Form::C32,64,64>": "igemm_kernel<64,64,2,2,c32>",
     "launch_one<Form::C32,128,32>": "igemm_kernel<128,32,4,1,c32>",
-    # wgrad_conv.hip wgrad_impl: the tiled weight-gradient kernel (RGB, bf16 storage, bf16 operands, exact fp32)
-    "launch_wgrad<64,64,2,2,1,true,true,true>": "wgrad_kernel<64,64,2,2,1,rgb,bf16hbm>",
-    "launch_wgrad<32,64,1,2,2,true,true,true>": "wgrad_kernel<32,64,1,2,2,rgb,bf16hbm>",
-    "launch_wgrad<64,64,2,2,1,true>": "wgrad_kernel<64,64,2,2,1,rgb>",
-    "launch_wgrad<32,64,1,2,2,true>": "wgrad_kernel<32,64,1,2,2,rgb>",
-    "launch_wgrad<128,128,2,2,1,false,true,true>": "wgrad_kernel<128,128,2,2,1,c32,bf16,bf16hbm>",
-    "launch_wgrad<64,64,2,2,1,false,true,true>": "wgrad_kernel<64,64,2,2,1,c32,bf16,bf16hbm>",
-    "launch_wgrad<64,32,2,1,2,false,true,true>": "wgrad_kernel<64,32,2,1,2,c32,bf16,bf16hbm>",
-    "launch_wgrad<32,64,1,2,2,false,true,true>": "wgrad_kernel<32,64,1,2,2,c32,bf16,bf16hbm>",
-    "launch_wgrad<32,32,1,1,4,false,false,true>": "wgrad_kernel<32,32,1,1,4,c32,bf16hbm>",
-    "launch_wgrad<128,128,2,2,1,false,true>": "wgrad_kernel<128,128,2,2,1,c32,bf16>",
-    "launch_wgrad<64,64,2,2,1,false,true>": "wgrad_kernel<64,64,2,2,1,c32,bf16>",
-    "launch_wgrad<64,32,2,1,2,false,true>": "wgrad_kernel<64,32,2,1,2,c32,bf16>",
-    "launch_wgrad<32,64,1,2,2,false,true>": "wgrad_kernel<32,64,1,2,2,c32,bf16>",
-    "launch_wgrad<128,128,2,2,1,false>": "wgrad_kernel<128,128,2,2,1,c32>",
-    "launch_wgrad<64,64,2,2,1,false>": "wgrad_kernel<64,64,2,2,1,c32>",
-    "launch_wgrad<64,32,2,1,2,false>": "wgrad_kernel<64,32,2,1,2,c32>",
-    "launch_wgrad<32,64,1,2,2,false>": "wgrad_kernel<32,64,1,2,2,c32>",
-    "launch_wgrad<32,32,1,1,4,false>": "wgrad_kernel<32,32,1,1,4,c32>",
-    # direct_conv.hip, stem_conv.hip, wgrad_conv.hip (all-taps and transpose-read forms)
+    # wgrad_conv.hip WGRAD_ROWS: one row per weight-gradient device kernel (tiled, transpose-read, all-taps 32 x 32 and 64 x 64)
+    "XV2_WGRAD_ROW(wgrad_kernel<WForm::RGB_BF16HBM,64,64>)": "wgrad_kernel<64,64,2,2,1,rgb,bf16hbm>",
+    "XV2_WGRAD_ROW(wgrad_kernel<WForm::RGB_BF16HBM,32,64>)": "wgrad_kernel<32,64,1,2,2,rgb,bf16hbm>",
+    "XV2_WGRAD_ROW(wgrad_kernel<WForm::RGB,64,64>)": "wgrad_kernel<64,64,2,2,1,rgb>",
+    "XV2_WGRAD_ROW(wgrad_kernel<WForm::RGB,32,64>)": "wgrad_kernel<32,64,1,2,2,rgb>",
+    "XV2_WGRAD_ROW(wgrad_kernel<WForm::BF16_BF16HBM,128,128>)": "wgrad_kernel<128,128,2,2,1,c32,bf16,bf16hbm>",
+    "XV2_WGRAD_ROW(wgrad_kernel<WForm::BF16_BF16HBM,64,64>)": "wgrad_kernel<64,64,2,2,1,c32,bf16,bf16hbm>",
+    "XV2_WGRAD_ROW(wgrad_kernel<WForm::BF16_BF16HBM,64,32>)": "wgrad_kernel<64,32,2,1,2,c32,bf16,bf16hbm>",
+    "XV2_WGRAD_ROW(wgrad_kernel<WForm::BF16_BF16HBM,32,64>)": "wgrad_kernel<32,64,1,2,2,c32,bf16,bf16hbm>",
+    "XV2_WGRAD_ROW(wgrad_kernel<WForm::C32_BF16HBM,32,32>)": "wgrad_kernel<32,32,1,1,4,c32,bf16hbm>",
+    "XV2_WGRAD_ROW(wgrad_kernel<WForm::BF16,128,128>)": "wgrad_kernel<128,128,2,2,1,c32,bf16>",
+    "XV2_WGRAD_ROW(wgrad_kernel<WForm::BF16,64,64>)": "wgrad_kernel<64,64,2,2,1,c32,bf16>",
+    "XV2_WGRAD_ROW(wgrad_kernel<WForm::BF16,64,32>)": "wgrad_kernel<64,32,2,1,2,c32,bf16>",
+    "XV2_WGRAD_ROW(wgrad_kernel<WForm::BF16,32,64>)": "wgrad_kernel<32,64,1,2,2,c32,bf16>",
+    "XV2_WGRAD_ROW(wgrad_kernel<WForm::C32,128,128>)": "wgrad_kernel<128,128,2,2,1,c32>",
+    "XV2_WGRAD_ROW(wgrad_kernel<WForm::C32,64,64>)": "wgrad_kernel<64,64,2,2,1,c32>",
+    "XV2_WGRAD_ROW(wgrad_kernel<WForm::C32,64,32>)": "wgrad_kernel<64,32,2,1,2,c32>",
+    "XV2_WGRAD_ROW(wgrad_kernel<WForm::C32,32,64>)": "wgrad_kernel<32,64,1,2,2,c32>",
+    "XV2_WGRAD_ROW(wgrad_kernel<WForm::C32,32,32>)": "wgrad_kernel<32,32,1,1,4,c32>",
+    "XV2_WGRAD_ROW(wgrad_tr_x3_kernel<128,128,3>)": "wgrad_tr_kernel<128,128,f32x3>",
+    "XV2_WGRAD_ROW(wgrad_tr_x3_kernel<64,64,3>)": "wgrad_tr_kernel<64,64,f32x3>",
+    "XV2_WGRAD_ROW(wgrad_tr_x3_kernel<128,128,2>)": "wgrad_tr_kernel<128,128,f16x2>",
+    "XV2_WGRAD_ROW(wgrad_tr_x3_kernel<64,64,2>)": "wgrad_tr_kernel<64,64,f16x2>",
+    "XV2_WGRAD_ROW(wgrad_tr_kernel<128,128>)": "wgrad_tr_kernel<128,128,bf16hbm>",
+    "XV2_WGRAD_ROW(wgrad_tr_kernel<64,64>)": "wgrad_tr_kernel<64,64,bf16hbm>",
+    "XV2_WGRAD_ROW(wgrad_alltaps_kernel<false>)": "wgrad_alltaps_kernel",
+    "XV2_WGRAD_ROW(wgrad_alltaps_kernel<true>)": "wgrad_alltaps_kernel<bf16>",
+    "XV2_WGRAD_ROW(wgrad_alltaps_tr_kernel)": "wgrad_alltaps_kernel<bf16hbm>",
+    "XV2_WGRAD_ROW(wgrad_alltaps_x3_kernel<3>)": "wgrad_alltaps_kernel<f32x3>",
+    "XV2_WGRAD_ROW(wgrad_alltaps_x3_kernel<2>)": "wgrad_alltaps_kernel<f16x2>",
+    "XV2_WGRAD_ROW(wgrad_alltaps64_tr_kernel)": "wgrad_alltaps64_kernel<bf16hbm>",
+    "XV2_WGRAD_ROW(wgrad_alltaps64_x3_kernel<3>)": "wgrad_alltaps64_kernel<f32x3>",
+    "XV2_WGRAD_ROW(wgrad_alltaps64_x3_kernel<2>)": "wgrad_alltaps64_kernel<f16x2>",
+    # direct_conv.hip, stem_conv.hip
     'prof_register("direct3x3_n32_kernel")': "direct3x3_n32_kernel",
     'prof_register("direct3x3_n32_kernel<bf16>")': "direct3x3_n32_kernel<bf16>",
     'prof_register("direct3x3_n32_kernel<bf16hbm>")': "direct3x3_n32_kernel<bf16hbm>",
@@ -103,17 +116,6 @@ VARIANTS = {
     'prof_register("direct3x3_n32_kernel<f16x2>")': "direct3x3_n32_kernel<f16x2>",
     'prof_register("stem7x7_kernel<rgb>")': "stem7x7_kernel<rgb>",
     'prof_register("stem7x7_wgrad_kernel<rgb>")': "stem7x7_wgrad_kernel<rgb>",
-    'prof_register("wgrad_alltaps_kernel")': "wgrad_alltaps_kernel",
-    'prof_register("wgrad_alltaps_kernel<bf16>")': "wgrad_alltaps_kernel<bf16>",
-    'prof_register("wgrad_alltaps_kernel<bf16hbm>")': "wgrad_alltaps_kernel<bf16hbm>",
-    'prof_register("wgrad_alltaps_kernel<f32x3>")': "wgrad_alltaps_kernel<f32x3>",
-    'prof_register("wgrad_alltaps_kernel<f16x2>")': "wgrad_alltaps_kernel<f16x2>",
-    'prof_register("wgrad_tr_kernel<128,128,f32x3>")': "wgrad_tr_kernel<128,128,f32x3>",
-    'prof_register("wgrad_tr_kernel<64,64,f32x3>")': "wgrad_tr_kernel<64,64,f32x3>",
-    'prof_register("wgrad_tr_kernel<128,128,f16x2>")': "wgrad_tr_kernel<128,128,f16x2>",
-    'prof_register("wgrad_tr_kernel<64,64,f16x2>")': "wgrad_tr_kernel<64,64,f16x2>",
-    'prof_register("wgrad_tr_kernel<128,128,bf16hbm>")': "wgrad_tr_kernel<128,128,bf16hbm>",
-    'prof_register("wgrad_tr_kernel<64,64,bf16hbm>")': "wgrad_tr_kernel<64,64,bf16hbm>",
     # thin_conv.hip (XV2_THIN_CASE and the transposed-convolution forms): the streaming 1x1 kernel and its 2x2 / 2 twins
     "thin_launch_one<64,64,true,2,2>": "thin1x1_kernel<64,64,bf16hbm>",
     "thin_launch_one<64,64,true,2,4>": "ablation-only: XV2_THIN_SUBS",
@@ -315,7 +317,12 @@ def _cases():
     # weight gradient: all-taps 3x3 form, transpose-read form (OW % 32 == 0), tiled kernel (every tile of its plan)
     for m in ("f32", "bf16m", "bf16s", "x3", "h2"):
         add(m + "-wgrad-alltaps", "wgrad", m, 2, 8, 32, 64, 128, k=3)
-    add("x3-wgrad-alltaps-96-dual", "wgrad", "x3", 1, 16, 32, 64, 96, k=3, C1=32)
+    # (Cout 96 rules out the 64 x 64 tile; two row chunks: the chunk-boundary halo rows, the second source)
+    for m in ("x3", "h2", "bf16s"):
+        add(m + "-wgrad-alltaps-96-dual", "wgrad", m, 1, 16, 32, 64, 96, k=3, C1=32)
+    # (64 x 64 tile, the second source selected by cn0 >= C0, three row chunks)
+    for m in ("x3", "h2", "bf16s"):
+        add(m + "-wgrad-alltaps64-dual", "wgrad", m, 1, 24, 32, 64, 128, k=3, C1=64)
     for m in ("x3", "h2", "bf16s"):
         add(m + "-wgrad-tr-128", "wgrad", m, 1, 4, 64, 128, 128)
         add(m + "-wgrad-tr-64", "wgrad", m, 1, 4, 64, 64, 192, k=3, s=2)
@@ -469,10 +476,15 @@ EXPECT = {
     'bf16s-rgb-wgrad-96': ('wgrad_kernel<32,64,1,2,2,rgb,bf16hbm>',),
     'f32-wgrad-alltaps': ('wgrad_alltaps_kernel',),
     'bf16m-wgrad-alltaps': ('wgrad_alltaps_kernel<bf16>',),
-    'bf16s-wgrad-alltaps': ('wgrad_alltaps_kernel<bf16hbm>',),
-    'x3-wgrad-alltaps': ('wgrad_alltaps_kernel<f32x3>',),
-    'h2-wgrad-alltaps': ('wgrad_alltaps_kernel<f16x2>',),
+    'bf16s-wgrad-alltaps': ('wgrad_alltaps64_kernel<bf16hbm>',),
+    'x3-wgrad-alltaps': ('wgrad_alltaps64_kernel<f32x3>',),
+    'h2-wgrad-alltaps': ('wgrad_alltaps64_kernel<f16x2>',),
     'x3-wgrad-alltaps-96-dual': ('wgrad_alltaps_kernel<f32x3>',),
+    'h2-wgrad-alltaps-96-dual': ('wgrad_alltaps_kernel<f16x2>',),
+    'bf16s-wgrad-alltaps-96-dual': ('wgrad_alltaps_kernel<bf16hbm>',),
+    'x3-wgrad-alltaps64-dual': ('wgrad_alltaps64_kernel<f32x3>',),
+    'h2-wgrad-alltaps64-dual': ('wgrad_alltaps64_kernel<f16x2>',),
+    'bf16s-wgrad-alltaps64-dual': ('wgrad_alltaps64_kernel<bf16hbm>',),
     'x3-wgrad-tr-128': ('wgrad_tr_kernel<128,128,f32x3>',),
     'x3-wgrad-tr-64': ('wgrad_tr_kernel<64,64,f32x3>',),
     'h2-wgrad-tr-128': ('wgrad_tr_kernel<128,128,f16x2>',),
