@@ -41,7 +41,8 @@ __global__ void __launch_bounds__(256) maxpool_fwd_kernel(const T* __restrict__ 
                 const float vv[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
                 for (int k = 0; k < 4; ++k)
-                    if (first || vv[k] > m[k]) {  // first maximum in scan order wins (torch CPU)
+                    // first maximum in scan order wins; a NaN wins and stays (torch CPU: (val > maxval) || isnan(val))
+                    if (first || vv[k] > m[k] || vv[k] != vv[k]) {
                         m[k] = vv[k];
                         am[k] = (uint8_t)(kh * 3 + kw);
                     }

@@ -1659,6 +1659,16 @@ class MaxPool3x3s2Fn(torch.autograd.Function):
         return dx, None
 
 
+def avgpool_out_size(L, k, s, pad, ceil_mode):
+    """output extent of torch's AvgPool2d along one axis: in ceil mode the last window must start inside the input or the
+    left padding"""
+    num = L + 2 * pad - k
+    o = (-(-num // s) if ceil_mode else num // s) + 1
+    if ceil_mode and (o - 1) * s >= L + pad:
+        o -= 1
+    return o
+
+
 class AvgPoolFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, k, s, pad, ceil_mode, count_include_pad, passthrough=False):
@@ -1667,14 +1677,7 @@ class AvgPoolFn(torch.autograd.Function):
         x_in = x
         x = x.contiguous()
         N, H, W, C = x.shape
-
-        def osz(L):
-            num = L + 2 * pad - k
-            o = (-(-num // s) if ceil_mode else num // s) + 1
-            if ceil_mode and (o - 1) * s >= L + pad:
-                o -= 1
-            return o
-        OH, OW = osz(H), osz(W)
+        OH, OW = avgpool_out_size(H, k, s, pad, ceil_mode), avgpool_out_size(W, k, s, pad, ceil_mode)
         y = _act((N, OH, OW, C), x)
         call("xv2_avgpool_forward", x, N, H, W, C, k, s, pad, 1 if count_include_pad else 0, OH, OW, y, _dt(x))
         ctx.cfg = (N, H, W, C, k, s, pad, 1 if count_include_pad else 0, OH, OW)
