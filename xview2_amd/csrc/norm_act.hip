@@ -1080,9 +1080,22 @@ static int column_sums(const ColOp<MODE, T>& op, int64_t npix, int C, double* su
     return reduce_stats<double>(dpart, g.chunks, C, sums, scratch, st, f0, f1);
 }
 
+// W-channel vector accesses of `esz`-byte elements (W * esz bytes, aligned)
+static inline bool vec_ok(int C, size_t esz, std::initializer_list<int> lds, std::initializer_list<const void*> ptrs,
+                          int W = 4) {
+    if (C % W) return false;
+    for (int l : lds)
+        if (l % W) return false;
+    for (const void* p : ptrs)
+        if (p && (reinterpret_cast<uintptr_t>(p) & (W * esz - 1))) return false;
+    return true;
+}
+
 extern "C" int xv2_bn_tensor_stats(const float* x, int ldx, int64_t npix, int C, double* sums, float* workspace,
                                    void* stream) {
     XV2_CHECK_ARG(npix > 0 && C > 0, "bn_tensor_stats: empty");
+    // the column form is chosen from C alone and the workspace was sized for it: rejected, not re-routed
+    XV2_CHECK_ARG(C % 4 != 0 || vec_ok(C, sizeof(float), {ldx}, {x}), "bn_tensor_stats: C %% 4 == 0 needs ldx %% 4 == 0 and a 16-byte aligned x");
     ColOp<0, float> op;
     op.a = x; op.lda = ldx; op.z = nullptr; op.y = nullptr; op.mean = nullptr; op.invstd = nullptr;
     op.scale = op.shift = nullptr;
@@ -1114,17 +1127,6 @@ extern "C" int xv2_bn_eval_coeffs(const float* gamma, const float* beta, const f
                        beta, running_mean, running_var, eps, scale, shift, C);
     XV2_CHECK_LAUNCH();
     return XV2_OK;
-}
-
-// W-channel vector accesses of `esz`-byte elements (W * esz bytes, aligned)
-static inline bool vec_ok(int C, size_t esz, std::initializer_list<int> lds, std::initializer_list<const void*> ptrs,
-                          int W = 4) {
-    if (C % W) return false;
-    for (int l : lds)
-        if (l % W) return false;
-    for (const void* p : ptrs)
-        if (p && (reinterpret_cast<uintptr_t>(p) & (W * esz - 1))) return false;
-    return true;
 }
 
 template <typename T>
@@ -1174,6 +1176,9 @@ static int bn_bwd_reduce_impl(const T* dz, int lddz, const T* z, int ldz, int zb
     XV2_CHECK_ARG(!zbits || (C % 4 == 0 && chunk_geom(npix, C, 4 * Vec16<T>::NV).cgw && act != XV2_ACT_SIGMOID),
                   "bn backward (mask form): unsupported channel count %d / activation", C);
     XV2_CHECK_ARG(C % 4 != 0 || (lddz % 4 == 0 && (!z || ldz % 4 == 0) && ldy % 4 == 0), "bn backward: strides must be multiples of 4");
+    // (pointers as well: the column form is chosen from C alone and the workspace was sized for it - rejected, not re-routed)
+    XV2_CHECK_ARG(C % 4 != 0 || (vec_ok(C, sizeof(T), {}, {dz, zbits ? nullptr : z, y}) && vec_ok(C, sizeof(float), {}, {mean, invstd, scale, shift})),
+                  "bn backward: C %% 4 == 0 needs operands aligned to 4 elements");
     XV2_CHECK_ARG(z || (scale && shift), "bn backward: either z or (scale, shift) is required for the activation mask");
     ColOp<1, T> op;
     op.a = dz; op.lda = lddz; op.z = z; op.ldz = ldz; op.y = y; op.ldy = ldy; op.mean = mean; op.invstd = invstd;
