@@ -502,6 +502,42 @@ size_t xv2_loss_workspace(int N, int C, int H, int W);
 int xv2_loss_backward(const float* logits, const uint8_t* labels, int N, int C, int H, int W,
                       int lstride, int post, int terms, const double* acc, const float* gscale,
                       float weight, float* dlogits, void* stream);
+/* ---- "ohem_hard": hard-negative mining with the selection the reference's Ohem intends (ohem.hip) --------
+ * Per image i of fp32 NCHW logits (C = 2 or 4) and uint8 labels sampled with `lstride` as above, with
+ * l = logsumexp(x) - x[y] per pixel: every positive (y > 0) is kept, of the Cn negatives (y == 0) the
+ * k = min(Cn, max(Cn / 4, 5, 2 Cp)) with the largest l.
+ *   loss = sum_i (sum of l over positives + sum of the k largest negative l) / sum_i (Cp + k).
+ * "ohem" is NOT this: it stays XV2_LOSS_CE, the mean CE the reference computes.  There is no `post` argument: behind
+ * the building mask every pixel is its own row with k >= 1, i.e. mean CE over building pixels (criterion.Loss sends
+ * that to XV2_LOSS_CE).
+ * Outputs, owned by the caller until the backward call has run:
+ *   px_loss[N*H*W]  l per pixel; positives hold the sentinel -1; zero is always +0 and NaN always 0x7fc00000, so
+ *                   the unsigned bit pattern of a negative's entry orders like its value, NaN above +Inf
+ *   records[N][8]   int32: Cp, Cn, k, bits(t), c_gt, c_eq, r, 0 with t the k-th largest negative loss, c_gt / c_eq
+ *                   the number of negatives with l > t / l == t and r = k - c_gt (all zero behind Cn when k == 0)
+ *   sums[3]         doubles: sum over positives, sum over selected negatives, number of samples sum_i (Cp + k)
+ *   loss[1]
+ * Tie rule: the loss does not depend on which r of the c_eq tied negatives are taken; the gradient gives each of
+ * them the weight r / c_eq (the mean over every valid choice), negatives above t the weight 1, below t 0:
+ *   dlogits = gscale[0] * w * (softmax - onehot) / sums[2].
+ * This differs from autograd through sort() only on exact ties.  A NaN loss among an image's negatives is its
+ * largest, is selected and makes the loss NaN.  The backward pass takes "above / at / below t" from px_loss and the
+ * record; it never evaluates l again.  Sums are fp32 inside a thread, fp64 across, in a fixed order; the selection
+ * is an exact radix select on integer counts: every output is bitwise reproducible.  9 launches forward, 1 backward,
+ * whatever N; nothing is read back.  M = H * W < 2^30, N <= 65535.                                              */
+size_t xv2_ohem_workspace(int N, int64_t M);
+int xv2_ohem_forward(const float* logits, const uint8_t* labels, int N, int C, int H, int W,
+                     int lstride, float* px_loss, int* records, double* sums, float* loss,
+                     void* workspace, void* stream);
+int xv2_ohem_backward(const float* logits, const uint8_t* labels, int N, int C, int H, int W,
+                      int lstride, const float* px_loss, const int* records, const double* sums,
+                      const float* gscale, float* dlogits, void* stream);
+/* The select stage alone: per row n of values[N][M], the k[n]-th largest (k device int32, clamped to 0..Cn) among
+ * the entries whose sign bit is clear (-0.0 counts as +0; every other entry with the sign bit set is skipped),
+ * ordered by bit pattern.  records as above with Cp = 0 and Cn = the number of candidates.  Workspace:
+ * xv2_ohem_workspace(N, M).                                                                                      */
+int xv2_topk_select(const float* values, int N, int64_t M, const int* k, int* records,
+                    void* workspace, void* stream);
 /* argmax over channels of NCHW logits (utils/f1.py:14,36): first maximum wins (torch.argmax) */
 int xv2_argmax_nchw(const float* logits, int N, int C, int64_t hw, int add, uint8_t* labels,
                     void* stream);

@@ -5,6 +5,14 @@ monai 0.4.0 losses with the constructor arguments of model/loss.py:11-13; ``mse`
 cross-entropy (the reference slices the (values, indices) tuple of ``sort`` at model/loss.py:45, so no
 negative is ever dropped).  All terms of one call share a single softmax pass; for ``--type post`` the
 building mask of model/loss.py:86-90 is applied inside the kernels (no compaction, order-independent sums).
+
+``ohem_hard`` is the hard-negative mining that ``ohem`` is named after, i.e. the reference's Ohem with the tuple slip
+repaired: per image every positive pixel (label > 0) and the k = min(Cn, max(Cn // 4, 5, 2 Cp)) negatives with the
+largest cross-entropy, summed over the batch and divided by the number of kept pixels (``ops.OhemFn``).  Negatives tied
+with the k-th largest loss share the remaining places: each gets the gradient weight r / c_eq (the mean over every valid
+choice of the tied subset), which differs from autograd through ``sort`` only on exact ties.  Under ``--type post`` the
+reference hands Ohem one row per building pixel, each keeps its single entry (k >= 1), so ``ohem_hard`` is mean CE over
+building pixels there and is routed to the CE bit.
 """
 import torch
 from torch import nn
@@ -21,7 +29,7 @@ class Loss(nn.Module):
         self.post = args.type == "post"
         self.names = self.loss_str.split("+")
         for n in self.names:
-            if n not in ("dice", "focal", "ce", "ohem", "mse", "coral"):
+            if n not in ("dice", "focal", "ce", "ohem", "ohem_hard", "mse", "coral"):
                 raise KeyError(n)
         # The reference special-cases loss_str == "mse" (float targets, model/loss.py:92-94) and builds the 3-logit coral head
         # only for loss_str == "coral" (model/unet.py:21-26): combined with other terms both fail in the reference's FIRST
@@ -43,8 +51,13 @@ class Loss(nn.Module):
         # the reference sums the terms one by one; duplicated names count twice
         total = None
         counts = {}
+        hard = 0
         for n in self.names:
-            counts[_TERM_BITS[n]] = counts.get(_TERM_BITS[n], 0) + 1
+            if n == "ohem_hard" and not self.post:
+                hard += 1
+                continue
+            b = ops.LOSS_CE if n == "ohem_hard" else _TERM_BITS[n]
+            counts[b] = counts.get(b, 0) + 1
         while counts:
             bits = 0
             for b in list(counts):
@@ -53,6 +66,9 @@ class Loss(nn.Module):
                 if counts[b] == 0:
                     del counts[b]
             part = ops.LossFn.apply(y_pred, y_true, bits, self.post, label_stride)
+            total = part if total is None else total + part
+        for _ in range(hard):
+            part = ops.OhemFn.apply(y_pred, y_true, label_stride)
             total = part if total is None else total + part
         return total
 

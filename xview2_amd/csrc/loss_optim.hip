@@ -9,6 +9,7 @@
 // Backward: a second streaming pass forms dL/dlogits analytically from acc[] (no autograd graph).
 #include "xv2_common.h"
 #include "optim_ctx.h"
+#include "loss_px.h"
 #include <algorithm>
 
 namespace xv2 {
@@ -16,33 +17,6 @@ namespace xv2 {
 constexpr int LOSS_BLOCKS = 1024;
 // acc layout (doubles): [0..3] I_c, [4..7] G_c, [8..11] P_c, [12] F, [13] E, [14] n
 constexpr int NACC = 15;
-
-template <int C>
-__device__ __forceinline__ void softmax_px(const float* __restrict__ logits, int64_t base, int64_t hw, float* p,
-                                           float& lse) {
-    float l[C];
-    float m = -INFINITY;
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-        l[c] = logits[base + c * hw];
-        m = fmaxf(m, l[c]);
-    }
-    float s = 0.f;
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-        p[c] = expf(l[c] - m);
-        s += p[c];
-    }
-    const float inv = 1.f / s;
-#pragma unroll
-    for (int c = 0; c < C; ++c) p[c] *= inv;
-    lse = m + logf(s);
-}
-
-__device__ __forceinline__ int label_at(const uint8_t* __restrict__ labels, int64_t n, int h, int w, int H, int W,
-                                        int ls) {
-    return labels[(n * (int64_t)H * ls + (int64_t)h * ls) * ((int64_t)W * ls) + (int64_t)w * ls];
-}
 
 template <int C>
 __global__ void __launch_bounds__(256) loss_fwd_kernel(const float* __restrict__ logits,

@@ -1928,6 +1928,58 @@ class LossFn(torch.autograd.Function):
         return d, None, None, None, None
 
 
+def ohem_forward(logits, labels, lstride=1):
+    """xv2_ohem_forward: (loss [1], px_loss [N, H*W], records [N, 8] int32, sums [3] float64, logits, labels), the last two
+    as handed to the kernels.  Every output is a fresh tensor; only the histogram workspace is scratch."""
+    _need_cuda(logits)
+    logits = logits.contiguous()
+    labels = labels.contiguous()
+    if labels.dtype != torch.uint8:
+        labels = labels.to(torch.uint8)
+    N, C, H, W = logits.shape
+    px_loss = _f32((N, H * W), logits)
+    rec = torch.empty((N, 8), dtype=torch.int32, device=logits.device)
+    sums = torch.empty((3,), dtype=torch.float64, device=logits.device)
+    loss = _f32((1,), logits)
+    ws = _ws(query("xv2_ohem_workspace", N, H * W), logits)
+    call("xv2_ohem_forward", logits, labels, N, C, H, W, lstride, px_loss, rec, sums, loss, ws)
+    return loss, px_loss, rec, sums, logits, labels
+
+
+class OhemFn(torch.autograd.Function):
+    """The ``ohem_hard`` term on NCHW logits (include/xv2.h, csrc/ohem.hip): all positives plus, per image, the
+    k = min(Cn, max(Cn // 4, 5, 2 Cp)) negatives with the largest cross-entropy, over the number of kept pixels.
+    The per-pixel losses, the per-image records and the sums belong to this node (deep supervision runs three forward
+    passes before the first backward, so they cannot live in shared scratch)."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, lstride):
+        loss, px_loss, rec, sums, logits, labels = ohem_forward(logits, labels, lstride)
+        ctx.save_for_backward(logits, labels, px_loss, rec, sums)
+        ctx.lstride = lstride
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, gout):
+        logits, labels, px_loss, rec, sums = ctx.saved_tensors
+        N, C, H, W = logits.shape
+        d = torch.empty_like(logits)
+        gs = gout.reshape(1).to(torch.float32).contiguous()
+        call("xv2_ohem_backward", logits, labels, N, C, H, W, ctx.lstride, px_loss, rec, sums, gs, d)
+        return d, None, None
+
+
+def topk_select(values, k):
+    """xv2_topk_select: values fp32 [N, M] and k int32 [N] on the device -> records [N, 8] int32 (Cp = 0): per row the
+    k-th largest entry among those with a clear sign bit (-0.0 is a zero), its tie counts and r"""
+    _need_cuda(values)
+    N, M = values.shape
+    rec = torch.empty((N, 8), dtype=torch.int32, device=values.device)
+    ws = _ws(query("xv2_ohem_workspace", N, M), values)
+    call("xv2_topk_select", values.contiguous(), N, M, k.to(torch.int32).contiguous(), rec, ws)
+    return rec
+
+
 # ------------------------------------------------------------------------------------------------
 # Input hand-over on the device (SURVEY 8f row 4).  The reference's datasets normalise uint8 HWC tiles on the host and
 # transpose them to CHW (data_loading/pytorch_loader.py:63,90-91,145-147); the kernels here are NHWC, so a tile can go
