@@ -538,6 +538,46 @@ int xv2_ohem_backward(const float* logits, const uint8_t* labels, int N, int C, 
  * xv2_ohem_workspace(N, M).                                                                                      */
 int xv2_topk_select(const float* values, int N, int64_t M, const int* k, int* records,
                     void* workspace, void* stream);
+/* ---- key sort (sort.hip) ------------------------------------------------------------------------------------------
+ * R independent rows of M uint32 keys, ascending: out[r][.] = sort(keys[r][.]).  A stable least-significant-digit radix
+ * sort, 8-bit digits, 4 passes of 3 launches (12 launches whatever R and M, rows on gridDim.y), nothing is read back.
+ * The sorted order of a key-only sort is unique, so every call gives the same bits.  out may be keys (in place);
+ * keys is otherwise left untouched.  1 <= R <= 65535, 1 <= M < 2^30; xv2_sort_workspace is 0 outside that.        */
+size_t xv2_sort_workspace(int R, int64_t M);
+int xv2_sort_u32(const uint32_t* keys, uint32_t* out, int R, int64_t M, void* workspace, void* stream);
+/* ---- "lovasz": the Lovasz-softmax loss (Berman et al., CVPR 2018, Algorithm 1; lovasz.hip) -----------------------
+ * classes = "present", per_image = False: the whole batch is one set per class.  fp32 NCHW logits (C = 2 or 4), uint8
+ * labels sampled with `lstride` as above, M = N * H * W < 2^30.  post == 0: a pixel's class is its label.  post != 0:
+ * pixels with label 0 are SKIPPED (in no class's set), the class is label - 1.  class_mask: bit c set = class c takes
+ * part in the mean (criterion.Loss: 0b10 for --type pre, the building class; 0b1111 for --type post).
+ * For class c: fg = (class == c), error e = 1 - p(c) if fg else p(c), p the channel softmax; G foreground and Nb
+ * background pixels.  With B_>(v) / b the background errors > v / == v and F_>=(v) the foreground errors >= v:
+ *   foreground weight  w = 1 / (G + B_>(e))
+ *   background weight  w = (G - F_>=(e)) / ((G + B_>(e)) (G + B_>(e) + b))
+ *   loss_c = sum e w,  loss = mean of loss_c over the classes of class_mask with G > 0 (0 when there is none)
+ * which is the sum of e_(j) (J_j - J_(j-1)) over the errors in descending order.  Tie rule: among equal errors the
+ * foreground comes first and the b tied background entries share their telescoped Jaccard increment equally, the mean
+ * over every order of the tied group: a valid subgradient that depends on no order.
+ * Outputs, owned by the caller until the backward call has run:
+ *   keys[C][M]     bits(e) | fg << 31; e is canonical (zero is +0, NaN the one pattern 0x7fc00000, above 1.0, which makes
+ *                  the loss NaN); skipped pixels hold 0xFFFFFFFF.  Written for every class.
+ *   sorted[C][M]   each row of keys ascending: background ascending, foreground ascending, skipped.  Written for the
+ *                  classes from the lowest to the highest one in class_mask; the other rows are not touched.
+ *   records[C][4]  int32: G, Nb, skipped, 1 if the class is in class_mask and G > 0 else 0
+ *   sums[5]        doubles: loss_c for c < C (0 for a class that is not included and present, and for c >= C), then
+ *                  sums[4] = n_present
+ *   loss[1]
+ * Backward: dlogit_k = gscale[0] * p_k (g_k - sum_c g_c p_c) with g_c = -w / n_present (foreground), +w / n_present
+ * (background), 0 for skipped pixels and classes that are not included and present.  It takes every comparison from the
+ * saved keys and the sorted rows, never from an error evaluated again.  Counts are integers, products and sums fp64 in a
+ * fixed order: every output is bitwise reproducible.  16 launches forward, 1 backward; nothing is read back.         */
+size_t xv2_lovasz_workspace(int N, int C, int H, int W);
+int xv2_lovasz_forward(const float* logits, const uint8_t* labels, int N, int C, int H, int W,
+                       int lstride, int post, unsigned class_mask, uint32_t* keys, uint32_t* sorted,
+                       int* records, double* sums, float* loss, void* workspace, void* stream);
+int xv2_lovasz_backward(const float* logits, int N, int C, int H, int W, const uint32_t* keys,
+                        const uint32_t* sorted, const int* records, const double* sums,
+                        const float* gscale, float* dlogits, void* stream);
 /* argmax over channels of NCHW logits (utils/f1.py:14,36): first maximum wins (torch.argmax) */
 int xv2_argmax_nchw(const float* logits, int N, int C, int64_t hw, int add, uint8_t* labels,
                     void* stream);

@@ -13,6 +13,12 @@ with the k-th largest loss share the remaining places: each gets the gradient we
 choice of the tied subset), which differs from autograd through ``sort`` only on exact ties.  Under ``--type post`` the
 reference hands Ohem one row per building pixel, each keeps its single entry (k >= 1), so ``ohem_hard`` is mean CE over
 building pixels there and is routed to the CE bit.
+
+``lovasz`` is the Lovasz-softmax loss (Berman et al., CVPR 2018, Algorithm 1; ``ops.LovaszFn``, csrc/lovasz.hip) with
+classes "present" over the whole batch: the convex extension of the Jaccard loss, which the xView2 F1 scores follow.
+``--type pre`` averages over the building class alone (dice drops the background for two channels the same way);
+``--type post`` over the four damage classes on building pixels, label 0 being in no class's set.  It is not in the
+reference's list; it is usually joined with a per-pixel term (``lovasz+ce``, ``focal+lovasz``).
 """
 import torch
 from torch import nn
@@ -29,7 +35,7 @@ class Loss(nn.Module):
         self.post = args.type == "post"
         self.names = self.loss_str.split("+")
         for n in self.names:
-            if n not in ("dice", "focal", "ce", "ohem", "ohem_hard", "mse", "coral"):
+            if n not in ("dice", "focal", "ce", "ohem", "ohem_hard", "lovasz", "mse", "coral"):
                 raise KeyError(n)
         # The reference special-cases loss_str == "mse" (float targets, model/loss.py:92-94) and builds the 3-logit coral head
         # only for loss_str == "coral" (model/unet.py:21-26): combined with other terms both fail in the reference's FIRST
@@ -51,10 +57,13 @@ class Loss(nn.Module):
         # the reference sums the terms one by one; duplicated names count twice
         total = None
         counts = {}
-        hard = 0
+        hard = lovasz = 0
         for n in self.names:
             if n == "ohem_hard" and not self.post:
                 hard += 1
+                continue
+            if n == "lovasz":
+                lovasz += 1
                 continue
             b = ops.LOSS_CE if n == "ohem_hard" else _TERM_BITS[n]
             counts[b] = counts.get(b, 0) + 1
@@ -69,6 +78,9 @@ class Loss(nn.Module):
             total = part if total is None else total + part
         for _ in range(hard):
             part = ops.OhemFn.apply(y_pred, y_true, label_stride)
+            total = part if total is None else total + part
+        for _ in range(lovasz):
+            part = ops.LovaszFn.apply(y_pred, y_true, label_stride, self.post)
             total = part if total is None else total + part
         return total
 

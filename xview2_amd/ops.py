@@ -1980,6 +1980,69 @@ def topk_select(values, k):
     return rec
 
 
+def sort_u32(keys):
+    """xv2_sort_u32: every row of `keys` ([M] or [R, M], int32 or uint32 storage, read as uint32) sorted ascending into a
+    fresh tensor of the same shape and dtype"""
+    _need_cuda(keys)
+    if keys.dtype not in (torch.int32, torch.uint32):
+        raise TypeError("sort_u32: int32 or uint32 keys, not %s" % keys.dtype)
+    keys = keys.contiguous()
+    R, M = (1, keys.shape[0]) if keys.dim() == 1 else keys.shape
+    out = torch.empty_like(keys)
+    ws = _ws(query("xv2_sort_workspace", R, M), keys)
+    call("xv2_sort_u32", keys, out, R, M, ws)
+    return out
+
+
+def lovasz_class_mask(C, post):
+    """the classes ``criterion.Loss`` averages over: the building class alone for two channels without the building mask
+    (as dice drops the background there), every class otherwise"""
+    return 0b10 if (C == 2 and not post) else (1 << C) - 1
+
+
+def lovasz_forward(logits, labels, lstride=1, post=False, class_mask=None):
+    """xv2_lovasz_forward: (loss [1], keys [C, N*H*W] int32, sorted [C, N*H*W] int32, records [C, 4] int32, sums [5] float64,
+    logits), the last as handed to the kernels.  Every output is a fresh tensor; only the workspace is scratch.  keys and
+    sorted hold uint32 bit patterns."""
+    _need_cuda(logits)
+    logits = logits.contiguous()
+    labels = labels.contiguous()
+    if labels.dtype != torch.uint8:
+        labels = labels.to(torch.uint8)
+    N, C, H, W = logits.shape
+    if class_mask is None:
+        class_mask = lovasz_class_mask(C, post)
+    keys = torch.empty((C, N * H * W), dtype=torch.int32, device=logits.device)
+    srt = torch.empty_like(keys)
+    rec = torch.empty((C, 4), dtype=torch.int32, device=logits.device)
+    sums = torch.empty((5,), dtype=torch.float64, device=logits.device)
+    loss = _f32((1,), logits)
+    ws = _ws(query("xv2_lovasz_workspace", N, C, H, W), logits)
+    call("xv2_lovasz_forward", logits, labels, N, C, H, W, lstride, 1 if post else 0, class_mask, keys, srt, rec, sums, loss, ws)
+    return loss, keys, srt, rec, sums, logits
+
+
+class LovaszFn(torch.autograd.Function):
+    """The ``lovasz`` term on NCHW logits (include/xv2.h, csrc/lovasz.hip): the Lovasz-softmax loss over the batch, classes
+    "present".  The keys, the sorted keys, the records and the sums belong to this node (deep supervision runs three
+    forward passes before the first backward, so they cannot live in shared scratch)."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, lstride, post):
+        loss, keys, srt, rec, sums, logits = lovasz_forward(logits, labels, lstride, post)
+        ctx.save_for_backward(logits, keys, srt, rec, sums)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, gout):
+        logits, keys, srt, rec, sums = ctx.saved_tensors
+        N, C, H, W = logits.shape
+        d = torch.empty_like(logits)
+        gs = gout.reshape(1).to(torch.float32).contiguous()
+        call("xv2_lovasz_backward", logits, N, C, H, W, keys, srt, rec, sums, gs, d)
+        return d, None, None, None
+
+
 # ------------------------------------------------------------------------------------------------
 # Input hand-over on the device (SURVEY 8f row 4).  The reference's datasets normalise uint8 HWC tiles on the host and
 # transpose them to CHW (data_loading/pytorch_loader.py:63,90-91,145-147); the kernels here are NHWC, so a tile can go
