@@ -578,7 +578,8 @@ int xv2_lovasz_forward(const float* logits, const uint8_t* labels, int N, int C,
 int xv2_lovasz_backward(const float* logits, int N, int C, int H, int W, const uint32_t* keys,
                         const uint32_t* sorted, const int* records, const double* sums,
                         const float* gscale, float* dlogits, void* stream);
-/* argmax over channels of NCHW logits (utils/f1.py:14,36): first maximum wins (torch.argmax) */
+/* argmax over channels of NCHW logits (utils/f1.py:14,36), equal to torch.argmax: the first maximum wins, a NaN is the
+ * maximum and the first NaN wins */
 int xv2_argmax_nchw(const float* logits, int N, int C, int64_t hw, int add, uint8_t* labels,
                     void* stream);
 /* F1 bookkeeping (utils/f1.py:27-47): counts[(c-1)*3 + {tp, fn, fp}] += ... for classes c = 1..n_class-1 over two

@@ -181,7 +181,8 @@ __global__ void __launch_bounds__(256) loss_aux_fwd_kernel(const float* __restri
         }
         const int64_t base = n * C * hw + q;
         if (MODE == 0) {
-            const float p = fmaxf(logits[base], 0.f);
+            const float x = logits[base];
+            const float p = x <= 0.f ? 0.f : x;      // relu that keeps a NaN (fmaxf would drop it: a finite loss of a NaN logit)
             const float d = p - (float)y;
             a += d * d;
         } else {
@@ -189,7 +190,9 @@ __global__ void __launch_bounds__(256) loss_aux_fwd_kernel(const float* __restri
             for (int k = 0; k < 3; ++k) {
                 const float x = logits[base + k * hw];
                 const float ls_ = fminf(x, 0.f) - log1pf(expf(-fabsf(x)));   // logsigmoid(x)
-                a -= (k < y) ? ls_ : (ls_ - x);
+                // 0 * x: +-0 for a finite x (the sum keeps its bits), NaN for x = +Inf on a reached level, where ls_ is 0 and the
+                // reference's logpt * levels + (logpt - x) * (1 - levels) is NaN as well: no finite loss of a non-finite logit
+                a -= (k < y) ? (ls_ + 0.f * x) : (ls_ - x);
             }
         }
         cnt += 1.f;
@@ -249,7 +252,8 @@ __global__ void argmax_kernel(const float* __restrict__ logits, int64_t total, i
 #pragma unroll
         for (int c = 1; c < C; ++c) {
             const float v = logits[(n * C + c) * hw + q];
-            if (v > best) {  // first maximum wins, like torch.argmax
+            // first maximum wins and a NaN is the maximum (the first NaN wins), like torch.argmax
+            if (v > best || (v != v && best == best)) {
                 best = v;
                 bi = c;
             }

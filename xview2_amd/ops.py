@@ -2283,7 +2283,7 @@ class CatChannelsFn(torch.autograd.Function):
 
 
 def argmax_labels(logits, add=0):
-    """bit-exact torch.argmax(logits, 1) (+add) as uint8 (utils/f1.py:14,36)."""
+    """bit-exact torch.argmax(logits, 1) (+add) as uint8, NaN logits included (utils/f1.py:14,36)."""
     _need_cuda(logits)
     logits = logits.contiguous()
     N, C, H, W = logits.shape

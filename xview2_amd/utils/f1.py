@@ -1,5 +1,5 @@
 """F1 bookkeeping of the reference's utils/f1.py on device: label maps come from the HIP argmax kernel
-(bit-exact torch.argmax: first maximum wins), tp/fp/fn are summed per class and all-reduced across ranks
+(bit-exact torch.argmax: first maximum wins, NaN is the maximum), tp/fp/fn are summed per class and all-reduced across ranks
 (``dist_reduce_fx="sum"`` in the reference, utils/f1.py:24-26)."""
 import torch
 import torch.distributed as dist
