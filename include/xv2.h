@@ -686,6 +686,22 @@ int xv2_grad_guard(const float* grad, int64_t n, float grad_scale, float max_nor
                    void* guard, void* stream);
 int xv2_optim_guard_ctx(const void* guard);
 
+/* Exponential moving average of the weights, taken right after any of the optimizer entry points above on the same flat buffer
+ * (a launch of its own: the rule kernels are not touched).  t = *count_dev, the updates applied so far, is read on the device;
+ *   d  = warmup ? min(decay, (1 + t) / (10 + t)) : decay        in double
+ *   om = (float)(1.0 - d)                                       the complement formed before the one rounding, like the betas
+ *   ema[i] = fmaf(om, param[i] - ema[i], ema[i])                one rounded subtraction, one fused multiply-add
+ * so param[i] == ema[i] leaves ema[i] bit for bit (but for the sign of a zero: an average of -0 comes back as +0, since
+ * (-0) - (-0) = +0 and +0 + -0 = +0) and a non-finite parameter reaches only its own element.  16-byte loads and
+ * stores when both pointers are 16-byte aligned, the same operations in a scalar loop for the tail and otherwise; the call's
+ * last launch increments *count_dev.  `guard` is NULL or the 64-byte record of xv2_grad_guard, passed explicitly (NOT through
+ * xv2_optim_guard_ctx): with its skip word set every kernel returns before touching anything - ema and *count_dev stay bit for
+ * bit, a skipped optimizer step neither pulls the average towards unchanged weights nor advances the warm-up; coef is ignored.
+ * decay and warmup are the only host values that enter, so a captured step that contains the call stays valid.
+ * n == 0: OK without a launch.  decay outside [0, 1) or NaN, n < 0, or n > 0 with a NULL pointer: XV2_EINVAL. */
+int xv2_ema_update_dev(float* ema, const float* param, int64_t n, double decay, int warmup, int* count_dev,
+                       const void* guard, void* stream);
+
 /* ---- in-library kernel timing (bench.py roofline leg) --------------------------------------
  * When enabled, every launch of an MFMA kernel (implicit-GEMM conv / weight-gradient) is bracketed
  * by hipEvents on its own stream and tagged with its algorithmic FLOP count (2*M*N*K of the

@@ -69,6 +69,9 @@ _LAUNCH_FLAGS = [
     # PL Trainer(gradient_clip_val) and its native-AMP GradScaler's step skipping (not flags of the reference's main.py)
     ("gradient_clip_val", dict(type=float, default=0.0, help="clip the global gradient norm to this value (0: off)")),
     ("skip_nonfinite", dict(action="store_true", help="skip (and count) an optimizer step whose gradient holds Inf / NaN")),
+    # an exponential moving average of the weights for validation, best.ckpt and evaluation (not flags of the reference's main.py)
+    ("ema_decay", dict(type=float, default=0.0, help="decay of the weight average that validation and best.ckpt use (0: off)")),
+    ("eval_ema", dict(action="store_true", help="--exec_mode eval: load the checkpoint's averaged weights (ema_state_dict)")),
     # synthetic-data knobs (not in the reference)
     ("train_size", dict(type=int, default=512)),
     ("eval_size", dict(type=int, default=1024)),
@@ -100,7 +103,7 @@ def main(argv=None):
         model = Model(args)
     else:
         assert args.ckpt is not None, "No checkpoint found for evaluation"
-        model = Model.load_from_checkpoint(args.ckpt)
+        model = Model.load_from_checkpoint(args.ckpt, ema=args.eval_ema)
         # the architecture comes from the checkpoint's hyper-parameters; run-time options come from this command
         for k in ("results", "logname", "tta", "val_batch_size", "seed"):
             setattr(model.args, k, getattr(args, k))
@@ -112,7 +115,7 @@ def main(argv=None):
                       sync_batchnorm=args.gpus > 1, accelerator="ddp" if args.gpus > 1 else None,
                       default_root_dir=args.results, checkpoint_callback=args.exec_mode == "train",
                       resume_from_checkpoint=checkpoint, gradient_clip_val=args.gradient_clip_val,
-                      skip_nonfinite=args.skip_nonfinite)
+                      skip_nonfinite=args.skip_nonfinite, ema_decay=args.ema_decay)
     if args.data == "synthetic":
         dm = SyntheticDataModule(args, device=trainer.device, rank=trainer.rank, train_size=args.train_size,
                                  eval_size=args.eval_size, steps_per_epoch=args.steps_per_epoch)

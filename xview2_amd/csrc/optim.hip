@@ -15,6 +15,9 @@
 // index order and writes the guard record (include/xv2.h): the clipped global norm's coefficient and the skip flag of a
 // non-finite gradient.  Every rule kernel is a template on GUARDED: that form multiplies the gradient scale by the record's
 // coefficient and returns before touching anything when the record says skip; the other form is the code without a guard.
+//
+// EMA of the weights (xv2_ema_update_dev): a kernel of its own behind the rule, never fused into one - one streaming launch over
+// the average and the parameter buffer plus the counter increment, with the guard record passed explicitly.
 #include "xv2_common.h"
 #include "optim_ctx.h"
 #include <algorithm>
@@ -445,6 +448,39 @@ __global__ void __launch_bounds__(256) grad_guard_fold_kernel(const double* __re
     if (isfinite(norm_f) && norm_f > guard[GUARD_NORM_MAX]) guard[GUARD_NORM_MAX] = norm_f;
 }
 
+// ---- EMA of the weights -----------------------------------------------------------------------------------------
+// ema += (1 - d) * (param - ema) over the flat parameter buffer: 12 bytes per element, one launch plus the counter increment.
+// d = min(decay, (1 + t) / (10 + t)) under warm-up, t the updates applied so far (read from the device), else decay; the
+// complement is formed in double and rounded once.  One rounded subtraction and one fused multiply-add per element, spelled
+// out so that the result does not hang on the compiler's contraction: param == ema is a fixed point bit for bit (an average
+// of -0 alone comes back as +0: +0 + -0 = +0), and a non-finite parameter reaches only its own element.
+__device__ __forceinline__ float ema_one(float e, float p, float om) { return fmaf(om, p - e, e); }
+
+template <bool GUARDED>
+__global__ void __launch_bounds__(256) ema_update_kernel(float* __restrict__ ema, const float* __restrict__ param, int64_t n,
+                                                          double decay, int warmup, const int* __restrict__ count_dev,
+                                                          const float* __restrict__ guard) {
+    if (GUARDED && reinterpret_cast<const int*>(guard)[GUARD_SKIP] != 0) return;     // a skipped step does not pull the average
+    double d = decay;
+    if (warmup) {
+        const double t = (double)count_dev[0];
+        d = fmin(decay, (1.0 + t) / (10.0 + t));
+    }
+    const float om = (float)(1.0 - d);
+    const int64_t n4 = ((reinterpret_cast<uintptr_t>(ema) | reinterpret_cast<uintptr_t>(param)) & 15) ? 0 : n >> 2;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+        float4 e = reinterpret_cast<float4*>(ema)[i];
+        const float4 p = reinterpret_cast<const float4*>(param)[i];
+        e.x = ema_one(e.x, p.x, om);
+        e.y = ema_one(e.y, p.y, om);
+        e.z = ema_one(e.z, p.z, om);
+        e.w = ema_one(e.w, p.w, om);
+        reinterpret_cast<float4*>(ema)[i] = e;
+    }
+    for (int64_t i = n4 * 4 + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        ema[i] = ema_one(ema[i], param[i], om);
+}
+
 }  // namespace xv2
 
 using namespace xv2;
@@ -581,4 +617,27 @@ extern "C" int xv2_novograd_step_dev(const int64_t* rows, int64_t rows_total, co
                        : novograd_launch<false>(rows, rows_total, tensors, ntensors, param, grad, exp_avg, norm_avg, partials,
                                                 lr_dev, step_dev, beta1, beta2, eps, weight_decay, grad_scale, nullptr,
                                                 (hipStream_t)stream);
+}
+
+extern "C" int xv2_ema_update_dev(float* ema, const float* param, int64_t n, double decay, int warmup, int* count_dev,
+                                  const void* guard, void* stream) {
+    XV2_CHECK_ARG(decay >= 0.0 && decay < 1.0, "ema_update_dev: decay = %g, must lie in [0, 1)", decay);
+    XV2_CHECK_ARG(n >= 0, "ema_update_dev: n = %lld, must not be negative", (long long)n);
+    if (n == 0) return XV2_OK;
+    XV2_CHECK_ARG(ema && param && count_dev, "ema_update_dev: null average, parameter buffer or counter");
+    // flat_rule_kernel's grid: one float4 per thread up to 4096 blocks, grid-stride beyond 4096 * 256 * 4 = 2^22 elements
+    const int grid = (int)std::min<int64_t>(cdiv(cdiv(n, 4), 256), 4096);
+    hipStream_t s = (hipStream_t)stream;
+    const float* g = static_cast<const float*>(guard);
+    if (g) {
+        hipLaunchKernelGGL(ema_update_kernel<true>, dim3(grid), dim3(256), 0, s, ema, param, n, decay, warmup, count_dev, g);
+        XV2_CHECK_LAUNCH();
+        hipLaunchKernelGGL(inc_step_kernel<true>, dim3(1), dim3(1), 0, s, count_dev, g);
+    } else {
+        hipLaunchKernelGGL(ema_update_kernel<false>, dim3(grid), dim3(256), 0, s, ema, param, n, decay, warmup, count_dev, g);
+        XV2_CHECK_LAUNCH();
+        hipLaunchKernelGGL(inc_step_kernel<false>, dim3(1), dim3(1), 0, s, count_dev, g);
+    }
+    XV2_CHECK_LAUNCH();
+    return XV2_OK;
 }

@@ -114,12 +114,15 @@ class Model(_Base):
         self.dllogger = _JsonLines(os.path.join(log_dir, log_name + ".json"))
 
     @classmethod
-    def load_from_checkpoint(cls, path, map_location="cpu"):
-        """the argparse Namespace rides in the checkpoint as its hyper-parameters, Lightning style (model/plt.py:23)"""
+    def load_from_checkpoint(cls, path, map_location="cpu", ema=False):
+        """the argparse Namespace rides in the checkpoint as its hyper-parameters, Lightning style (model/plt.py:23).
+        ema=True loads the averaged weights a run with --ema_decay wrote (`ema_state_dict`) in place of `state_dict`."""
         blob = torch.load(path, map_location=map_location, weights_only=False)
+        if ema and "ema_state_dict" not in blob:
+            raise KeyError("%s holds no ema_state_dict (it was written without --ema_decay)" % path)
         hyper = blob["hyper_parameters"]
         model = cls(hyper["args"] if isinstance(hyper, dict) and "args" in hyper else hyper)
-        model.load_state_dict(blob["state_dict"])
+        model.load_state_dict(blob["ema_state_dict" if ema else "state_dict"])
         return model
 
     # ---- forward / steps ----------------------------------------------------------------------------------------

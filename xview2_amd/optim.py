@@ -5,7 +5,12 @@ the device step-counter increment.
 All parameters are re-pointed at views of a single fp32 buffer and their ``.grad`` at views of a second one,
 so (a) the optimizer step is a single streaming kernel over the parameter, gradient and state arrays, (b) the
 data-parallel reducer (xview2_amd.dist) all-reduces contiguous slices without packing copies.
+
+``FlatEMA`` keeps an exponential moving average of that parameter buffer (one more launch per step) that validation,
+``best.ckpt`` and evaluation can be taken from.
 """
+import contextlib
+
 import torch
 
 from . import ops
@@ -310,6 +315,100 @@ class FlatNovoGrad(_FlatSegmented):
         call("xv2_novograd_step_dev", self.rows, self.rows.shape[0], self.tensors, len(self.params), self.flat_p,
              self.flat_g, self.exp_avg, self.exp_avg_norm, self.partials, self.lr_dev, self.step_dev,
              float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.weight_decay), grad_scale)
+
+
+class FlatEMA:
+    """Exponential moving average of a FlatOptimizer's parameter buffer (include/xv2.h xv2_ema_update_dev): `ema` has
+    flat_p's layout, padding included, and starts as a copy of it; `count_dev` counts the updates on the device.  Under
+    --precision 16 flat_p holds the fp32 master weights, so the average is one of fp32 masters.
+
+    The average covers the trainable parameters only.  Buffers (the BatchNorm running statistics, num_batches_tracked)
+    are already averages of their own: the model computes with its live buffers inside applied(), and
+    model_state_dict() passes them on as they are.
+
+    decay d, warmup: the effective decay of update t (from 0) is min(d, (1 + t) / (10 + t)), so that the first updates
+    are not dominated by the initial weights; warmup=False uses d throughout."""
+
+    def __init__(self, optimizer, decay, warmup=True):
+        if not isinstance(optimizer, FlatOptimizer):
+            raise TypeError("FlatEMA averages the flat buffer of a FlatOptimizer, not %s" % type(optimizer).__name__)
+        decay = float(decay)
+        if not (0.0 <= decay < 1.0):
+            raise ValueError("decay = %r: must lie in [0, 1)" % decay)
+        if not optimizer.capturable:
+            raise RuntimeError("FlatEMA updates on the GPU only (HIP kernels; there is no CPU fallback)")
+        self.optimizer, self.decay, self.warmup = optimizer, decay, bool(warmup)
+        self.ema = optimizer.flat_p.clone()
+        self.count_dev = torch.zeros(1, dtype=torch.int32, device=self.ema.device)
+        self._applied = False
+
+    def update(self):
+        """one call on the current stream, right after optimizer.step(...): the optimizer's guard record rides along, so
+        a skipped step leaves the average and the counter alone"""
+        if self._applied:
+            raise RuntimeError("FlatEMA.update() inside applied(): the parameters hold the average itself")
+        from ._capi import call
+        o = self.optimizer
+        call("xv2_ema_update_dev", self.ema, o.flat_p, o.total, self.decay, int(self.warmup), self.count_dev, o.guard)
+
+    @torch.no_grad()
+    def _exchange(self):
+        """the contents of flat_p and ema change places (the parameters stay the same views), then the invalidation the
+        optimizer's step uses: every cached layout of the old weights is stale"""
+        o = self.optimizer
+        tmp = o.flat_p.clone()
+        o.flat_p.copy_(self.ema)
+        self.ema.copy_(tmp)
+        self._applied = not self._applied
+        ops.weights_changed()
+        ops.repack_all()
+
+    @contextlib.contextmanager
+    def applied(self):
+        """inside, the model computes with the averaged weights through the ordinary HIP path; on the way out (also when
+        the body raised) the exchange is undone and training continues as if the context had never been entered"""
+        if self._applied:
+            raise RuntimeError("FlatEMA.applied() is already entered")
+        self._exchange()
+        try:
+            yield self
+        finally:
+            self._exchange()
+
+    def _slices(self, model):
+        """(name, tensor, offset or None) per state_dict entry: the offset into the flat buffer of every tensor that lives
+        in flat_p, by address - which covers the names FusedUNet registers twice"""
+        o = self.optimizer
+        base, end = o.flat_p.data_ptr(), o.flat_p.data_ptr() + 4 * o.total
+        for k, v in model.state_dict().items():
+            inside = v.dtype == torch.float32 and v.numel() > 0 and v.device == o.flat_p.device and base <= v.data_ptr() < end
+            yield k, v, (v.data_ptr() - base) // 4 if inside else None
+
+    def model_state_dict(self, model):
+        """the model's state_dict() with every tensor that lives in flat_p replaced by its slice of the average (views,
+        as state_dict()'s own).  Trainable parameters only: buffers (BatchNorm running statistics, num_batches_tracked)
+        are taken as they are - they are averages of their own already."""
+        src = self.optimizer.flat_p if self._applied else self.ema
+        return {k: (v if off is None else src[off:off + v.numel()].view(v.shape)) for k, v, off in self._slices(model)}
+
+    def state_dict(self):
+        """{"decay", "warmup", "updates"}; `updates` is read from the device (this synchronises)"""
+        return {"decay": self.decay, "warmup": self.warmup, "updates": int(self.count_dev.item())}
+
+    @torch.no_grad()
+    def load_state_dict(self, sd, ema_state_dict=None, model=None):
+        """restores the device counter and, given an EMA state dict (model_state_dict's product) and the model, the
+        buffer by parameter name.  decay and warmup stay what this object was built with."""
+        if self._applied:
+            raise RuntimeError("FlatEMA.load_state_dict() inside applied()")
+        self.count_dev.fill_(int(sd["updates"]))
+        if ema_state_dict is None:
+            return
+        if model is None:
+            raise ValueError("FlatEMA.load_state_dict: the buffer is restored by parameter name and needs the model")
+        for k, v, off in self._slices(model):
+            if off is not None:
+                self.ema[off:off + v.numel()].view(v.shape).copy_(ema_state_dict[k])
 
 
 def make_flat_optimizer(name, params, lr, weight_decay=0.0, momentum=0.0):

@@ -11,19 +11,22 @@ import os
 import torch
 
 from . import dist as xdist
-from .optim import FlatOptimizer
+from .optim import FlatEMA, FlatOptimizer
 
 
 class Trainer:
     def __init__(self, gpus=1, precision=32, max_epochs=1, min_epochs=None, sync_batchnorm=False, accelerator=None,
                  default_root_dir=".", resume_from_checkpoint=None, checkpoint_callback=True, callbacks=None,
                  benchmark=True, deterministic=False, num_sanity_val_steps=0, logger=False, log_every=0,
-                 gradient_clip_val=0.0, skip_nonfinite=False):
+                 gradient_clip_val=0.0, skip_nonfinite=False, ema_decay=0.0):
         self.gpus, self.max_epochs, self.root = gpus, max_epochs, default_root_dir
         # PL's gradient_clip_val (global-norm clipping, 0 = off) and the step skipping of its native-AMP GradScaler: the flat
         # optimizer's gradient guard (optim.FlatOptimizer.set_guard).  guard_log: one dict per epoch when a guard is set.
         self.gradient_clip_val, self.skip_nonfinite = float(gradient_clip_val), bool(skip_nonfinite)
         self.guard_log = []
+        # > 0: an exponential moving average of the weights (optim.FlatEMA), updated after every optimizer step; validation, the
+        # score that selects best.ckpt and the checkpoints' ema_state_dict are taken from it.  0: off, nothing changes.
+        self.ema_decay, self.ema = float(ema_decay), None
         self.sync_batchnorm, self.resume = sync_batchnorm, resume_from_checkpoint
         self.checkpointing = bool(checkpoint_callback)
         self.log_every = log_every
@@ -48,12 +51,16 @@ class Trainer:
         if isinstance(optimizer, FlatOptimizer):
             ckpt["optimizer_states"] = [{k: (v.cpu() if torch.is_tensor(v) else v)
                                          for k, v in optimizer.state_dict().items()}]
+        if self.ema is not None:
+            # state_dict stays the live weights (resume continues from them); the averaged ones ride next to it
+            ckpt["ema_state_dict"] = {k: v.detach().cpu() for k, v in self.ema.model_state_dict(model).items()}
+            ckpt["ema"] = self.ema.state_dict()
         torch.save(ckpt, path)
 
     # ------------------------------------------------------------------ fit
     def fit(self, model, datamodule):
         model.to(self.device)
-        start_epoch = 0
+        start_epoch, ckpt = 0, None
         # the loader (dataset index, worker pool, sampler) is built once; its length is this rank's steps per epoch
         train_loader = datamodule.train_dataloader()
         try:
@@ -84,6 +91,15 @@ class Trainer:
             if not flat:
                 raise RuntimeError("gradient_clip_val / skip_nonfinite need a flat optimizer (xview2_amd.optim)")
             optimizer.set_guard(self.gradient_clip_val, self.skip_nonfinite)
+        self.ema = None
+        if self.ema_decay > 0.0:
+            if not flat:
+                raise RuntimeError("ema_decay needs a flat optimizer (xview2_amd.optim)")
+            # (after a resume has loaded the weights: without an average in the file it starts from them, counter 0)
+            self.ema = FlatEMA(optimizer, self.ema_decay)
+            if ckpt is not None and "ema" in ckpt and "ema_state_dict" in ckpt:
+                self.ema.load_state_dict(ckpt["ema"], ckpt["ema_state_dict"], model)
+        ckpt = None
         seen = {"steps": 0, "clipped": 0, "skipped": 0}
         reducer = xdist.GradReducer(optimizer, sync_bn=self.sync_batchnorm or self.world > 1) if flat else None
         frozen = False
@@ -100,6 +116,8 @@ class Trainer:
                 loss.backward()
                 if flat:
                     optimizer.step(reducer.finish())
+                    if self.ema is not None:
+                        self.ema.update()
                 else:
                     optimizer.step()
                 if scheduler is not None:
@@ -117,8 +135,13 @@ class Trainer:
             xdist.check_peer_exchange()          # one-shot SyncBatchNorm exchange: a timed-out exchange is an error, per epoch
             if guarded:
                 self._report_guard(model, optimizer, epoch, seen)
-            score = self.validate(model, datamodule)
-            if guarded:
+            if self.ema is not None:
+                model.epoch_extras = dict(getattr(model, "epoch_extras", None) or {}, ema=True)
+                with self.ema.applied():         # f1 / val_loss and the score that selects best.ckpt: the averaged weights'
+                    score = self.validate(model, datamodule)
+            else:
+                score = self.validate(model, datamodule)
+            if guarded or self.ema is not None:
                 model.epoch_extras = None
             if self.checkpointing:
                 ckdir = os.path.join(self.root, "checkpoints")
