@@ -825,6 +825,32 @@ int xv2_label_components(const uint8_t* mask, int B, int H, int W, void* workspa
 int xv2_xview2_counts(const uint8_t* lp, const uint8_t* dp, const uint8_t* lt, const uint8_t* dt, int B, int64_t hw,
                       int64_t* counts, void* stream);
 
+/* ---- scene inference: windows of a scene of any size, blended on the device (xview2_amd/scene.py, scene.hip) ---------
+ * A scene is H x W pixels, H * W < 2^30.  Windows are h x w (multiples of 32, 32..2048) with their origins (y0, x0) in a
+ * device table; the table's order is the summation order.  tri(i, L) is reflection without repeating the edge, iterated:
+ * period 2 (L - 1), tri(i, 1) = 0 (np.pad(mode="reflect")).  ramp r(i) = min(i + 1, n - i, overlap + 1) along an axis of
+ * window side n; a window pixel weighs r(iy) * r(ix).  Origins are clamped into the scene on the device (a corrupt table
+ * reads a wrong pixel, never another allocation). */
+#define XV2_SCENE_SIGMOID1 0  /* C = 2: sigmoid(channel 1)      -> 1 map   (Model._decode, --type pre)   */
+#define XV2_SCENE_SOFTMAX  1  /* softmax over C channels        -> C maps  (damage heads)                */
+#define XV2_SCENE_SIGMOID  2  /* sigmoid per channel            -> C maps  (coral, C = 3)                */
+#define XV2_SCENE_RELU     3  /* max(x, 0)                      -> C maps  (mse, C = 1)                  */
+#define XV2_SCENE_MAX_WINDOWS 1024   /* windows per call (the table is held in LDS) */
+/* out[k][iy][ix][:] = pre[tri(y0 + iy, H)][tri(x0 + ix, W)][0..2] (then post's three channels when post != NULL): uint8
+ * [K][h][w][3 | 6], the layout ops.DeviceImage normalises.  pre / post: uint8 [H][W][3].  out must be 4-byte aligned. */
+int xv2_scene_windows_u8(const uint8_t* pre, const uint8_t* post, int H, int W, const int32_t* origins, int K, int h, int w,
+                         uint8_t* out, void* stream);
+/* acc[c][y][x] = fmaf(r(iy) r(ix), p_c, acc[c][y][x]) for every window of the table that holds scene pixel (y, x), in table
+ * order, p = the decode `kind` of that window's logits [K][C][h][w] at (y - y0, x - x0); window positions at or past H / W
+ * (padding) are dropped.  One thread owns a scene pixel: no atomics, and the same bits however a scene's windows are split
+ * over calls in the same order.  C: 2 (SIGMOID1), 2..5 (SOFTMAX), 1..5 (SIGMOID, RELU).  0 <= overlap <= min(h, w) / 2.
+ * acc: fp32 [Cout][H][W], zeroed by the caller once per scene. */
+int xv2_scene_blend(const float* logits, int kind, int C, const int32_t* origins, int K, int h, int w, int overlap, int H,
+                    int W, float* acc, void* stream);
+/* acc[c][y][x] /= (float)(wy[y] * wx[x]) in place (a division, no reciprocal): wy [H], wx [W] the per-axis sums of the ramps
+ * (scene.axis_normaliser); their product is below 2^24. */
+int xv2_scene_finalize(float* acc, int Cout, int H, int W, const int32_t* wy, const int32_t* wx, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,132 @@
+"""Apply a trained pair of checkpoints to imagery of any size that has no labels.
+
+    python -m xview2_amd.predict --ckpt_loc loc.ckpt --ckpt_dmg dmg.ckpt --pre pre.png --post post.png --out DIR
+
+--pre / --post take a file or a directory; directories are paired by sorted order and must hold equally many files.  Each
+pair is predicted window by window on the GPU (xview2_amd.scene) and written as <stem>_localization_prediction.png and
+<stem>_damage_prediction.png, <stem> being the pre image's; --save_probs adds the blended maps as .npy.  With only one
+checkpoint only its map is written: the localization map is then the 0.3 threshold of post-processing, the damage map the
+decoded class of every pixel."""
+import os
+from argparse import ArgumentDefaultsHelpFormatter, ArgumentParser
+
+import numpy as np
+
+IMAGE_SUFFIXES = (".png", ".jpg", ".jpeg", ".tif", ".tiff", ".bmp")
+
+
+def get_parser():
+    parser = ArgumentParser(prog="python -m xview2_amd.predict", formatter_class=ArgumentDefaultsHelpFormatter)
+    arg = parser.add_argument
+    arg("--ckpt_loc", type=str, default=None, help="localization checkpoint (--type pre)")
+    arg("--ckpt_dmg", type=str, default=None, help="damage checkpoint (--type post)")
+    arg("--pre", type=str, required=True, help="pre-disaster image, or a directory of them")
+    arg("--post", type=str, default=None, help="post-disaster image or directory (required with --ckpt_dmg)")
+    arg("--out", type=str, required=True, help="directory the predictions are written to")
+    arg("--window", type=int, default=1024, help="window side (a multiple of 32, 32..2048)")
+    arg("--overlap", type=int, default=256, help="pixels two neighbouring windows share (at most half the window)")
+    arg("--batch", type=int, default=4, help="windows per model call")
+    arg("--tta", action="store_true", help="average every window over the identity and three flips")
+    arg("--precision", type=int, default=16, choices=[16, 32], help="32: exact fp32; 16: bf16 matrix math")
+    arg("--ema", action="store_true", help="load the checkpoints' averaged weights (ema_state_dict)")
+    arg("--components", action="store_true", help="majority damage class per connected building")
+    arg("--dilate", action="store_true", help="dilate both maps")
+    arg("--dilation_rate", type=int, default=3, help="dilation rate (odd)")
+    arg("--save_probs", action="store_true", help="also write the blended probability maps as .npy")
+    return parser
+
+
+def _listing(path):
+    if os.path.isdir(path):
+        return sorted(os.path.join(path, f) for f in os.listdir(path) if f.lower().endswith(IMAGE_SUFFIXES))
+    if not os.path.exists(path):
+        raise FileNotFoundError(path)
+    return [path]
+
+
+def pair_inputs(pre, post=None):
+    """[(pre file, post file | None)]: directories are paired by sorted order with equal counts"""
+    pres = _listing(pre)
+    if not pres:
+        raise ValueError("no image under %s" % pre)
+    if post is None:
+        return [(p, None) for p in pres]
+    posts = _listing(post)
+    if len(pres) != len(posts):
+        raise ValueError("%d pre images under %s but %d post images under %s" % (len(pres), pre, len(posts), post))
+    return list(zip(pres, posts))
+
+
+def read_bgr(path):
+    """cv2.imread semantics, as data_loading/pytorch_loader.py load_pair: 8-bit B, G, R"""
+    from PIL import Image
+    return np.ascontiguousarray(np.asarray(Image.open(path).convert("RGB"))[:, :, ::-1])
+
+
+def _load(path, ema, tta, device):
+    from .lightning import Model
+    model = Model.load_from_checkpoint(path, ema=ema)
+    model.args.tta = tta
+    return model.to(device).eval()
+
+
+def main(argv=None):
+    args = get_parser().parse_args(argv)
+    if args.ckpt_loc is None and args.ckpt_dmg is None:
+        raise ValueError("give --ckpt_loc, --ckpt_dmg or both")
+    if args.ckpt_dmg is not None and args.post is None:
+        raise ValueError("--ckpt_dmg needs --post")
+    import torch
+    from PIL import Image
+    from . import ops, scene
+    from .utils.post_process import post_process_tiles
+    scene.check_window(args.window, args.overlap)
+    pairs = pair_inputs(args.pre, args.post if args.ckpt_dmg is not None else None)
+    if not torch.cuda.is_available():
+        raise RuntimeError("xview2_amd.predict runs on the MI355X only; there is no CPU fallback")
+    device = torch.device("cuda", torch.cuda.current_device())
+    # the arithmetic mode, as Trainer.__init__ sets it
+    ops.MATH_MODE = ops.MATH_BF16 if args.precision == 16 else ops.fp32_math()
+    ops.set_storage_dtype(torch.bfloat16 if args.precision == 16 else None)
+    loc = dmg = None
+    if args.ckpt_loc is not None:
+        loc = scene.ScenePredictor(_load(args.ckpt_loc, args.ema, args.tta, device), args.window, args.overlap, args.batch)
+        if loc.kind != scene.SIGMOID1:
+            raise ValueError("%s is no localization (--type pre) checkpoint" % args.ckpt_loc)
+    if args.ckpt_dmg is not None:
+        dmg = scene.ScenePredictor(_load(args.ckpt_dmg, args.ema, args.tta, device), args.window, args.overlap, args.batch)
+        if dmg.kind == scene.SIGMOID1:
+            raise ValueError("%s is no damage (--type post) checkpoint" % args.ckpt_dmg)
+    os.makedirs(args.out, exist_ok=True)
+    for pre_path, post_path in pairs:
+        pre = read_bgr(pre_path)
+        post = read_bgr(post_path) if post_path is not None else None
+        if post is not None and post.shape != pre.shape:
+            raise ValueError("%s is %d x %d but %s is %d x %d" % (pre_path, pre.shape[0], pre.shape[1], post_path,
+                                                                   post.shape[0], post.shape[1]))
+        stem = os.path.join(args.out, os.path.splitext(os.path.basename(pre_path))[0])
+        pre_d = torch.from_numpy(pre).to(device)
+        post_d = torch.from_numpy(post).to(device) if post is not None else None
+        H, W, _ = pre.shape
+        loc_maps = loc.predict(pre_d) if loc is not None else None
+        dmg_maps = dmg.predict(pre_d, post_d) if dmg is not None else None
+        # a missing partner is neutral in the fusion: every pixel a building / no pixel damaged beyond class 1
+        loc_map = loc_maps[0] if loc is not None else torch.ones((H, W), dtype=torch.float32, device=device)
+        dmg_map = (scene.decode_damage(dmg_maps, dmg.kind) if dmg is not None
+                   else torch.ones((H, W), dtype=torch.int32, device=device))
+        pre_png, post_png = post_process_tiles(loc_map, dmg_map, args.components and dmg is not None, args.dilate,
+                                               args.dilation_rate)
+        if loc is not None:
+            Image.fromarray(pre_png.cpu().numpy()).save(stem + "_localization_prediction.png")
+        if dmg is not None:
+            Image.fromarray(post_png.cpu().numpy()).save(stem + "_damage_prediction.png")
+        if args.save_probs:
+            if loc is not None:
+                np.save(stem + "_localization_probs.npy", loc_maps.cpu().numpy())
+            if dmg is not None:
+                np.save(stem + "_damage_probs.npy", dmg_maps.cpu().numpy())
+    return len(pairs)
+
+
+if __name__ == "__main__":
+    print("predicted %d scenes" % main())
