@@ -825,6 +825,30 @@ int xv2_label_components(const uint8_t* mask, int B, int H, int W, void* workspa
 int xv2_xview2_counts(const uint8_t* lp, const uint8_t* dp, const uint8_t* lt, const uint8_t* dt, int B, int64_t hw,
                       int64_t* counts, void* stream);
 
+/* ---- per-building table of a prediction (buildings.hip, xview2_amd/utils/buildings.py) -------------------------------
+ * labels: int32 [B,H,W] as xv2_label_components writes them; dmg: uint8 [B,H,W]; loc: fp32 [B,H,W] or NULL.
+ * count[b] (int32 [B]) = the number of components of tile b, the true number even above max_rows.  rows: int64
+ * [B][max_rows][16]; rows 0 .. min(count[b], max_rows) - 1 are written, in ascending order of column 0 (scipy.ndimage.label's
+ * numbering for 4-connectivity); nothing else of rows is touched.  count is overwritten by every call; neither it nor the
+ * workspace needs clearing.  Columns:
+ *   0        root: label - 1, the linear index y * W + x of the component's first pixel in raster order
+ *   1        area in pixels
+ *   2..5     ymin, xmin, ymax, xmax (inclusive)
+ *   6, 7     sum of y, sum of x over the component's pixels
+ *   8..11    pixels whose dmg is 1, 2, 3, 4
+ *   12       pixels whose dmg is anything else (0, or > 4)
+ *   13       the class 1..4 with the largest of columns 8..11, ties to the smaller class (pp_vote_kernel's rule); 0 when all
+ *            four are 0
+ *   14       sum of q(loc), q(v) = __float2int_rn(fminf(fmaxf(v, 0.f), 1.f) * 65535.f) in fp32 (NaN -> 0); 0 when loc is NULL
+ *   15       0
+ * Every column is an integer and every reduction an integer add, min or max: the same bits on every run.  Five launches,
+ * nothing is read back.  Size limits as xv2_postprocess (H * W < 2^30, B <= 65535), max_rows >= 1; the workspace query is 0
+ * outside them.  A label that names no root of its tile is dropped (it adds to no row). */
+#define XV2_BUILDING_COLS 16
+size_t xv2_building_table_workspace(int B, int H, int W);
+int xv2_building_table(const int32_t* labels, const uint8_t* dmg, const float* loc, int B, int H, int W, int max_rows,
+                       void* workspace, int64_t* rows, int32_t* count, void* stream);
+
 /* ---- scene inference: windows of a scene of any size, blended on the device (xview2_amd/scene.py, scene.hip) ---------
  * A scene is H x W pixels, H * W < 2^30.  Windows are h x w (multiples of 32, 32..2048) with their origins (y0, x0) in a
  * device table; the table's order is the summation order.  tri(i, L) is reflection without repeating the edge, iterated:

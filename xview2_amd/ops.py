@@ -2387,3 +2387,40 @@ def xview2_counts(lp, dp, lt, dt):
     counts = torch.zeros((B, 16), dtype=torch.int64, device=lp.device)
     call("xv2_xview2_counts", *maps, B, hw, counts)
     return counts
+
+
+# ---- per-building table of a prediction (csrc/buildings.hip) -----------------------------------------------------------
+BUILDING_COLS = 16
+
+
+def building_table(labels, dmg, loc=None, max_rows=None):
+    """One int64 row of 16 columns per 4-connected component (include/xv2.h xv2_building_table).  labels: int32 [B,H,W] as
+    label_components writes them; dmg: uint8 [B,H,W]; loc: fp32 [B,H,W] or None.  max_rows: row capacity per tile (default
+    max(1024, H*W // 256)).  Returns (rows int64 [B, max_rows, 16], count int32 [B]) on the device; only rows
+    0 .. min(count[b], max_rows) - 1 of a tile are written, count[b] is the true number of components."""
+    _need_cuda(labels)
+    _need_cuda(dmg)
+    if labels.dim() != 3 or labels.dtype != torch.int32:
+        raise ValueError("building_table: labels must be int32 [B,H,W], got %s %s" % (labels.dtype, tuple(labels.shape)))
+    if dmg.dtype != torch.uint8 or dmg.shape != labels.shape:
+        raise ValueError("building_table: dmg must be uint8 %s, got %s %s" % (tuple(labels.shape), dmg.dtype,
+                                                                             tuple(dmg.shape)))
+    if loc is not None:
+        _need_cuda(loc)
+        if loc.dtype != torch.float32 or loc.shape != labels.shape:
+            raise ValueError("building_table: loc must be fp32 %s, got %s %s" % (tuple(labels.shape), loc.dtype,
+                                                                                tuple(loc.shape)))
+        loc = loc.contiguous()
+    B, H, W = labels.shape
+    max_rows = max(1024, H * W // 256) if max_rows is None else int(max_rows)
+    if max_rows < 1:
+        raise ValueError("building_table: max_rows must be at least 1, got %d" % max_rows)
+    labels, dmg = labels.contiguous(), dmg.contiguous()
+    need = int(query("xv2_building_table_workspace", int(B), int(H), int(W)))
+    if need == 0:
+        raise ValueError("building_table: B=%d H=%d W=%d outside the supported sizes (H*W < 2^30, B <= 65535)" % (B, H, W))
+    ws = _ws(need, labels)
+    rows = torch.empty((B, max_rows, BUILDING_COLS), dtype=torch.int64, device=labels.device)
+    count = torch.empty((B,), dtype=torch.int32, device=labels.device)
+    call("xv2_building_table", labels, dmg, loc, B, H, W, max_rows, ws, rows, count)
+    return rows, count

@@ -6,7 +6,8 @@
 pair is predicted window by window on the GPU (xview2_amd.scene) and written as <stem>_localization_prediction.png and
 <stem>_damage_prediction.png, <stem> being the pre image's; --save_probs adds the blended maps as .npy.  With only one
 checkpoint only its map is written: the localization map is then the 0.3 threshold of post-processing, the damage map the
-decoded class of every pixel."""
+decoded class of every pixel.  --buildings adds <stem>_buildings.csv (one row per predicted building: box, area, centroid,
+damage class, pixel counts, confidence) and <stem>_buildings.json (totals), computed on the GPU (xview2_amd.utils.buildings)."""
 import os
 from argparse import ArgumentDefaultsHelpFormatter, ArgumentParser
 
@@ -33,6 +34,7 @@ def get_parser():
     arg("--dilate", action="store_true", help="dilate both maps")
     arg("--dilation_rate", type=int, default=3, help="dilation rate (odd)")
     arg("--save_probs", action="store_true", help="also write the blended probability maps as .npy")
+    arg("--buildings", action="store_true", help="also write <stem>_buildings.csv / .json: one row per predicted building")
     return parser
 
 
@@ -120,6 +122,13 @@ def main(argv=None):
             Image.fromarray(pre_png.cpu().numpy()).save(stem + "_localization_prediction.png")
         if dmg is not None:
             Image.fromarray(post_png.cpu().numpy()).save(stem + "_damage_prediction.png")
+        if args.buildings:
+            # from the maps the PNGs show (after --components and --dilate); confidence only with a localization model
+            from .utils import buildings
+            rows = buildings.building_table(pre_png, post_png, loc_map if loc is not None else None)
+            records = buildings.to_records(rows, H, W, confidence=loc is not None)
+            buildings.write_csv(stem + "_buildings.csv", records)
+            buildings.write_summary(stem + "_buildings.json", records)
         if args.save_probs:
             if loc is not None:
                 np.save(stem + "_localization_probs.npy", loc_maps.cpu().numpy())

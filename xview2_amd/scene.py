@@ -185,10 +185,15 @@ def decode_damage(maps, kind):
     raise ValueError("decode_damage: kind %r is no damage decode" % (kind,))
 
 
-def predict_pair(loc, dmg, pre_u8, post_u8, components=False, dilate=False, dilation_rate=3):
+def predict_pair(loc, dmg, pre_u8, post_u8, components=False, dilate=False, dilation_rate=3, buildings=False):
     """loc, dmg: ScenePredictors of a localization and a damage model -> (uint8 [H, W] localization, uint8 [H, W] damage),
-    through utils.post_process.post_process_tiles at scene size"""
+    through utils.post_process.post_process_tiles at scene size.  buildings=True: a third value, the int64 [n, 16] table of
+    the buildings the two maps show (utils.buildings.building_table, confidence from the blended localization map)."""
     from .utils.post_process import post_process_tiles
     loc_map = loc.predict(pre_u8)[0]
     dmg_map = decode_damage(dmg.predict(pre_u8, post_u8), dmg.kind)
-    return post_process_tiles(loc_map, dmg_map, components, dilate, dilation_rate)
+    pre, post = post_process_tiles(loc_map, dmg_map, components, dilate, dilation_rate)
+    if not buildings:
+        return pre, post
+    from .utils.buildings import building_table
+    return pre, post, building_table(pre, post, loc_map)

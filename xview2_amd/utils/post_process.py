@@ -18,7 +18,10 @@ Semantics are the reference's (post_process.py:27-47), bit for bit, with these d
      output: 0..255 without --components, 1..4 with it (the vote keeps four classes per building); otherwise
      ValueError, where the reference would vote over it and write a PNG its scorer rejects.
 
-    python -m xview2_amd.utils.post_process --results R [--components] [--dilate [--dilation_rate 3]]
+    python -m xview2_amd.utils.post_process --results R [--components] [--dilate [--dilation_rate 3]] [--buildings]
+
+--buildings also writes buildings/test_buildings_NNNNN.csv per pair: one row per predicted building of the two PNGs
+(xview2_amd.utils.buildings), its confidence from the localization probabilities.
 """
 import os
 from argparse import ArgumentDefaultsHelpFormatter, ArgumentParser, ArgumentTypeError
@@ -79,6 +82,11 @@ def _out_name(path):
     return os.path.basename(path).replace(".npy", "_prediction.png")
 
 
+def _buildings_name(pre_path):
+    base = os.path.basename(pre_path)
+    return (base[:-4] if base.endswith(".npy") else base).replace("localization", "buildings") + ".csv"
+
+
 def post_process(args, pre_path, post_path):
     """one pair of .npy files -> two prediction PNGs under <args.results>/predictions (reference signature)"""
     results = getattr(args, "results", "/results")
@@ -120,6 +128,13 @@ def run(args):
                     workspace[key] = ops.postprocess_workspace(len(ks), lshape[0], lshape[1], args.components, dev)
                 pre, post = ops.postprocess(loc, dmg, components=args.components, rate=rate,
                                             workspace=workspace.get(key))
+                if getattr(args, "buildings", False):
+                    from . import buildings
+                    os.makedirs(os.path.join(args.results, "buildings"), exist_ok=True)
+                    for j, rows in enumerate(buildings.building_table(pre, post, loc)):
+                        recs = buildings.to_records(rows, lshape[0], lshape[1])
+                        pending.append(pool.submit(buildings.write_csv, os.path.join(
+                            args.results, "buildings", _buildings_name(pairs[ks[j]][0])), recs))
                 pre, post = pre.cpu().numpy(), post.cpu().numpy()
                 for j, k in enumerate(ks):
                     a, b = pairs[k]
@@ -145,6 +160,7 @@ def get_parser():
     arg("--dilation_rate", type=int, default=3, help="Dilation rate (odd)")
     arg("--results", type=str, default="/results", help="Directory holding probs/; predictions/ is written there")
     arg("--batch", type=_positive_int, default=8, help="Tiles per GPU call")
+    arg("--buildings", action="store_true", help="Also write buildings/<name>.csv per pair: one row per predicted building")
     return parser
 
 
