@@ -99,7 +99,7 @@ int xv2_pack_weights_table(const int64_t* table, int n, int64_t total_tiles, voi
  * AND remembers the pair: convolutions handed `b_fp32` afterwards read the planes, so the caller must refresh them on the
  * same stream whenever the packed weights change (xv2_presplit_table: all pairs of a device table [n][6] int64 =
  * {b_fp32, x3 (pointers), nrows, T, ctot, first block} in one launch, an entry owns xv2_presplit_blocks() blocks) and call
- * xv2_presplit_forget(b_fp32) before releasing either buffer (NULL: forget every pair).  XV2_PRESPLIT=0 ignores the pairs. */
+ * xv2_presplit_forget(b_fp32) before releasing either buffer (NULL: forget every pair). */
 /* RGB stem (model/unet.py:45 enc_l1: the 7x7 / stride-2 convolution over the image) as a "band" convolution: a KH x KW
  * (KW <= 8) kernel over the 4-channel image equals a KH x 1 kernel over 32 "channels" = the floats of eight consecutive
  * pixels of a row.  xv2_pad_band copies the NHWC4 image into a zero-padded frame [N][IHp][IWp][4] (fp32 or bf16, image at
@@ -438,7 +438,7 @@ int xv2_rsoftmax_backward(const float* att, const float* datt, float* dlogits, i
  * column-sum partials that xv2_splat_gap_forward would take from z, written to `workspace` (xv2_splat_gap_workspace bytes) -
  * bit-identical partials, no second pass over z, one launch per block less; xv2_splat_gap_finish folds them into gap.
  * xv2_conv_bn_act_forward_grouped(gap_part != NULL) runs it as the layer's apply pass; xv2_splat_tail_forward(gap_ready = 1) then
- * skips the column-sum launch.  XV2_SPLAT_FUSE bit 2 (default on) switches it for A/B runs. */
+ * skips the column-sum launch. */
 int xv2_bn_act_gap_supported(int C);
 int xv2_bn_act_gap_forward(const void* y, const float* scale, const float* shift, int act, void* z, int N, int64_t hw,
                            int C, float* workspace, int dtype, void* stream);

@@ -7,7 +7,7 @@
 REPS=${1:-6}; TAG=${2:-crowd}
 OUT=gpurun_out/${TAG}_stress.txt
 echo "crowding stress: $REPS repetitions x 6 xdist workers on one GPU ($(date -u +%FT%TZ), commit $(git rev-parse --short HEAD 2>/dev/null))" > $OUT
-echo "environment: XV2_BN_FOLD=${XV2_BN_FOLD:-unset(off)} XV2_SG=${XV2_SG:-unset(on)} XV2_F16X2=${XV2_F16X2:-unset(on)}" >> $OUT
+echo "environment: XV2_SG=${XV2_SG:-unset(on)} XV2_F16X2=${XV2_F16X2:-unset(on)}" >> $OUT
 FAILS=0
 for r in $(seq 1 $REPS); do
   python -m pytest tests/test_model_gpu.py tests/test_sg_conv_gpu.py tests/test_f16x2_gpu.py tests/test_coop_gpu.py -m gpu -q -n 6 \

@@ -1,5 +1,5 @@
 #!/bin/bash
-# like pmc_abl.sh but with an environment assignment instead of a library:  scripts/pmc_env.sh XV2_HALO=1 [layer] [fwd|dgrad]
+# like pmc_abl.sh but with an environment assignment instead of a library:  scripts/pmc_env.sh XV2_HALO_BF16=0 [layer] [fwd|dgrad]
 R=$PWD
 cd /tmp && export TMPDIR=/tmp
 L=${2:-dec2}; W=${3:-fwd}; F=${4:-igemm_kernel}

@@ -200,7 +200,7 @@ def registered_name(key):
 def test_variant_table_lists_exactly_the_instantiations_of_the_conv_sources():
     from tests.test_conv_variants_gpu import VARIANTS
     src = set(source_variants(_texts()))
-    assert len(src) >= 118
+    assert len(src) >= 112
     assert set(VARIANTS) == src, ("in the sources, not in VARIANTS: %s" % sorted(src - set(VARIANTS)),
                                   "in VARIANTS, not in the sources: %s" % sorted(set(VARIANTS) - src))
 
@@ -215,7 +215,7 @@ def test_an_added_instantiation_is_caught():
                                 "tiled_lds(64, 32), 2, 2, X_IN, wgrad_kernel<WForm::C32_BF16HBM, 64, 32>)\n#undef XV2_WGRAD_ROW\n")
     added = set(source_variants(texts)) - set(VARIANTS)
     assert added == {"launch_one<Form::F32X3,64,32>", "XV2_WGRAD_ROW(wgrad_kernel<WForm::C32_BF16HBM,64,32>)", "thin_launch_one<32,64,true,2,2>",
-                     "thin_launch_one<32,64,true,2,4>", "thin_launch_one<32,64,false,4,4,0,2>", "thin_launch_one<32,64,false,4,4>",
+                     "thin_launch_one<32,64,false,4,4,0,2>", "thin_launch_one<32,64,false,4,4>",
                      "sg_launch_one<2,2,2,true,true>", "sg_launch_one<2,2,2,false,true>", "sg_launch_one<2,2,2,true,false>",
                      "sg_launch_one<2,2,2,false,false>"}, sorted(added)
 

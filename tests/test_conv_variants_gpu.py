@@ -118,29 +118,23 @@ VARIANTS = {
     'prof_register("stem7x7_wgrad_kernel<rgb>")': "stem7x7_wgrad_kernel<rgb>",
     # thin_conv.hip (XV2_THIN_CASE and the transposed-convolution forms): the streaming 1x1 kernel and its 2x2 / 2 twins
     "thin_launch_one<64,64,true,2,2>": "thin1x1_kernel<64,64,bf16hbm>",
-    "thin_launch_one<64,64,true,2,4>": "ablation-only: XV2_THIN_SUBS",
     "thin_launch_one<64,64,false,4,4,0,2>": "thin1x1_kernel<64,64,f16x2>",
     "thin_launch_one<64,64,false,4,4>": "thin1x1_kernel<64,64,f32x3>",
     "thin_launch_one<64,128,true,2,2>": "thin1x1_kernel<64,128,bf16hbm>",
-    "thin_launch_one<64,128,true,2,4>": "ablation-only: XV2_THIN_SUBS",
     "thin_launch_one<64,128,false,4,4,0,2>": "thin1x1_kernel<64,128,f16x2>",
     "thin_launch_one<64,128,false,4,4>": "thin1x1_kernel<64,128,f32x3>",
     "thin_launch_one<64,256,true,2,2>": "thin1x1_kernel<64,256,bf16hbm>",
-    "thin_launch_one<64,256,true,2,4>": "ablation-only: XV2_THIN_SUBS",
     "thin_launch_one<64,256,false,4,4,0,2>": "thin1x1_kernel<64,256,f16x2>",
     "thin_launch_one<64,256,false,4,4>": "thin1x1_kernel<64,256,f32x3>",
     "thin_launch_one<128,64,true,2,2>": "thin1x1_kernel<128,64,bf16hbm>",
-    "thin_launch_one<128,64,true,2,4>": "ablation-only: XV2_THIN_SUBS",
     "thin_launch_one<128,64,false,4,4,0,2>": "thin1x1_kernel<128,64,f16x2>",
     "thin_launch_one<128,64,false,4,4>": "thin1x1_kernel<128,64,f32x3>",
     "thin_launch_one<256,64,true,2,2>": "thin1x1_kernel<256,64,bf16hbm>",
-    "thin_launch_one<256,64,true,2,4>": "ablation-only: XV2_THIN_SUBS",
     "thin_launch_one<256,64,false,4,4,0,2>": "thin1x1_kernel<256,64,f16x2>",
     "thin_launch_one<256,64,false,4,4>": "thin1x1_kernel<256,64,f32x3>",
     "thin_launch_one<64,128,true,2,2,1>": "thin_convT_fwd<64,32,bf16hbm>",
     "thin_launch_one<64,128,false,4,4,1>": "thin_convT_fwd<64,32,f32x3>",
     "thin_launch_one<128,64,true,2,2,2>": "thin_convT_bwd<32,64,bf16hbm>",
-    "thin_launch_one<128,64,false,4,4,2>": "ablation-only: XV2_THIN_CT",
     # sg_conv.hip (XV2_SG_CASE): the small-grid kernel per configuration (rows, columns, wave groups), 1x1 / per-tap form and
     # storage; the 128-row configuration serves only statistics plans of 128-row tiles, which no default plan asks for
     "sg_launch_one<2,2,4,true,true>": "sg_conv_kernel<64,128,g2,1x1,bf16hbm>",

@@ -443,7 +443,7 @@ def test_bottleneck_shortcut_gradient_is_summed_in_the_dgrad_epilogue(downsample
     close(nchw(out), ref, 2e-5, "out")
     if thin:
         # 4 M activations: a handful of pre-activations sit within rounding of zero and their ReLU masks flip against the
-        # CPU evaluation (the tiled kernels show the same 4e-3 outliers, XV2_THIN=0); each flip moves one pixel's gradient
+        # CPU evaluation (the tiled kernels showed the same 4e-3 outliers); each flip moves one pixel's gradient
         err = (nchw(leaf.grad).double() - xr.grad.double()).abs() / xr.grad.abs().max().item()
         assert float((err > 5e-5).float().mean()) < 1e-3 and float(err.max()) < 5e-2
     else:
@@ -679,8 +679,8 @@ def test_bf16_storage_stem_residual_convt_pool_head():
     old = ops.STORAGE
     ops.set_storage_dtype(torch.bfloat16)
     try:
-        # RGB stems: fp32 image in, bf16 activations out - the torchvision 7x7 / stride 2 stem (a band convolution,
-        # ops.STEM_BAND) and the first 3x3 / stride 2 convolution of the ResNeSt deep stem (32 or 64 outputs; gather kernel -
+        # RGB stems: fp32 image in, bf16 activations out - the torchvision 7x7 / stride 2 stem (a band convolution)
+        # and the first 3x3 / stride 2 convolution of the ResNeSt deep stem (32 or 64 outputs; gather kernel -
         # as a band convolution it measured 0.194 -> 0.099 ms alone and nothing on the cfg3 step: frame copy + weight pack)
         for co, k, pad in ((64, 7, 3), (32, 3, 1), (64, 3, 1)):
             x = torch.randn(2, 3, 40, 36)
@@ -844,7 +844,7 @@ def test_presplit_weight_planes_are_the_exact_three_way_split():
     set).  Undoing the layout and adding hi + mid + lo in fp32 must give the packed fp32 operand back BIT FOR BIT (the split
     is exact: 8 + 8 + 8 significant bits), for the forward (OHWI) and the backward-data (IHWO) operand."""
     from xview2_amd import ops
-    if ops.MATH_MODE != ops.MATH_F32X3 or not ops.PRESPLIT:
+    if ops.MATH_MODE != ops.MATH_F32X3:
         pytest.skip("pre-split planes are made under XV2_MATH_F32X3 only")
     torch.manual_seed(5)
     Cout, Cin = 128, 192         # both layouts need 64-row units and 32-channel chunks
@@ -877,7 +877,7 @@ def test_f16x2_weight_planes_hold_the_scaled_weights_to_22_bits():
     every weight within 2^18 of the maximum), and the three-plane copies are not made for such an entry"""
     import ctypes
     from xview2_amd import ops
-    if ops.MATH_MODE != ops.MATH_F32X3 or not ops.PRESPLIT or not ops.F16X2:
+    if ops.MATH_MODE != ops.MATH_F32X3 or not ops.F16X2:
         pytest.skip("the two-plane copies are made under XV2_MATH_F32X3 with F16X2 on")
     torch.manual_seed(6)
     Cout, Cin = 128, 192
@@ -945,13 +945,12 @@ print("halo ok %%.2e" %% worst)
 
 
 def test_halo_form_of_the_f32x3_kernel_in_a_subprocess():
-    """igemm_kernel<..., HALO> (XV2_HALO=1, read once per process): 3x3 forward and backward-data with the 10 x 18 halo of
-    every 16-channel slice resident in LDS for all nine taps.  Opt-in after measurement; this keeps it exact."""
+    """igemm_kernel<..., HALO> (the form these layers take): 3x3 forward and backward-data with the 10 x 18 halo of every
+    16-channel slice resident in LDS for all nine taps, in a process of its own.  This keeps it exact."""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, XV2_HALO="1")
-    r = subprocess.run([sys.executable, "-c", HALO_SNIPPET % root], env=env, capture_output=True, text=True, timeout=600)
+    r = subprocess.run([sys.executable, "-c", HALO_SNIPPET % root], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "halo ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
 
 

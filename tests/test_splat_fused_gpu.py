@@ -96,7 +96,7 @@ def test_splat_conv_block_of_the_model_path_against_pytorch(shape, training):
 @pytest.mark.parametrize("shape", [(2, 16, 16, 64, 32), (2, 8, 8, 256, 128), (3, 12, 20, 128, 64), (8, 4, 4, 512, 256)])
 def test_tail_backward_with_two_launches_less_is_bitwise_the_op_by_op_chain(shape):
     """xv2_splat_tail_backward since round 6 - datt's fold + rSoftMax's backward in one launch, both products of each dense layer's
-    backward in one problem-indexed launch (XV2_SPLAT_FUSE bits 3 and 4) - against the public op-level entry points: the fold
+    backward in one problem-indexed launch - against the public op-level entry points: the fold
     launch followed by xv2_rsoftmax_backward (bit for bit), the dense layer's weight / bias gradient from the separate kernel
     (dx = NULL call: bit for bit) and its input gradient against an fp64 product."""
     from xview2_amd._capi import call, query

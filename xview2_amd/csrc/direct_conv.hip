@@ -366,9 +366,7 @@ int direct3x3_launch(const IgemmParams& p, hipStream_t stream) {
     int grid = std::min(npatches, x3 ? 256 : p.math == XV2_MATH_BF16_STORE ? 1024 : 512);
     IgemmParams q = p;
     const bool h2 = x3 && f16x2_ready_pertap(q);      // F16X2: maxima of the source and of the weights known
-    static const bool own_pass = [] { const char* e = getenv("XV2_AMAX_PASS"); return e && atoi(e) == 1; }();      // A/B runs: the round-5 form
-    if (own_pass) q.amax_out = nullptr;
-    else if (p.amax_out && p.amax_recorded && p.math != XV2_MATH_BF16_STORE) *p.amax_recorded = 1;      // (the kernel's epilogue records)
+    if (p.amax_out && p.amax_recorded && p.math != XV2_MATH_BF16_STORE) *p.amax_recorded = 1;      // (the kernel's epilogue records)
     const double flops = 2.0 * (double)c.M * 32.0 * 9.0 * p.Ctot;
     const double abytes = (p.math == XV2_MATH_BF16_STORE ? 2.0 : 4.0) *
                           ((double)c.M * p.Ctot + 32.0 * 9.0 * p.Ctot + (double)c.M * 32.0);

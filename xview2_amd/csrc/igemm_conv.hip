@@ -54,12 +54,6 @@ static int launch_one(const IgemmParams& p, hipStream_t stream) {
     return XV2_OK;
 }
 
-// planner knob (tuning sweeps): K-tiles' worth of work charged per split-K block for writing / re-reading its slab
-static double slab_cost(double dflt) {
-    static const double v = [] { const char* e = getenv("XV2_SLAB_COST"); return e ? atof(e) : -1.0; }();
-    return v >= 0.0 ? v : dflt;
-}
-
 // tile shape and split-K factor; `nkt` = K tiles of the (single-class) problem, 0 disables split-K
 static void pick_tile(int64_t M, int Nout, bool smallc, int nkt, int math, int& bm, int& bn, int& ksplit) {
     bn = (Nout % 128 == 0) ? 128 : (Nout % 64 == 0 ? 64 : 32);
@@ -102,9 +96,9 @@ static void pick_tile(int64_t M, int Nout, bool smallc, int nkt, int math, int& 
             bm = 64;
         }
         if (bn == 128 && nkt >= 16) {
-            static const int ks_max_h = [] { const char* e = getenv("XV2_KSPLIT_MAX"); return e ? atoi(e) : 8; }();
-            for (int ks = 2; ks <= ks_max_h && nkt / ks >= 8; ++ks) {
-                const double c = cost(cdiv(M, 128) * ntn * ks, 128.0, (double)cdiv(nkt, ks) + slab_cost(12.0), 1.0);
+            // (+ 12 K-tiles' worth of work per split-K block for writing / re-reading its slab, as below)
+            for (int ks = 2; ks <= 8 && nkt / ks >= 8; ++ks) {
+                const double c = cost(cdiv(M, 128) * ntn * ks, 128.0, (double)cdiv(nkt, ks) + 12.0, 1.0);
                 if (c < best * 0.95) {
                     best = c;
                     bm = 128;
@@ -123,23 +117,21 @@ static void pick_tile(int64_t M, int Nout, bool smallc, int nkt, int math, int& 
     // (6-12 MFMAs per stage and barrier; measured 143 vs 190 TFLOP/s on the 116-GFLOP decoder layers)
     // (64-channel outputs, round 3: 128 x 64 measured 5 % FASTER than 64 x 64 at equal rounds - dec4.c1 132 vs 126, l1.conv2 104
     //  vs 98 TFLOP/s - so there the 64-row tile only wins when it needs fewer rounds)
-    static const double eff64_x3 = [] { const char* e = getenv("XV2_EFF64"); return e ? atof(e) : 0.65; }();      // (A/B runs)
-    const double eff64 = math == XV2_MATH_F32X3 ? (bn == 64 ? 0.48 : eff64_x3) : 0.92;
+    const double eff64 = math == XV2_MATH_F32X3 ? (bn == 64 ? 0.48 : 0.65) : 0.92;
     const double c64 = rounds(cdiv(M, 64) * ntn, cap64) * 64.0 * k / eff64;
     if (c64 < best * 0.97) {
         best = c64;
         bm = 64;
     }
-    static const int ks_max = [] { const char* e = getenv("XV2_KSPLIT_MAX"); return e ? atoi(e) : 8; }();   // A/B runs
     if (bn == 128 && nkt >= 16) {
         const int64_t blocks128 = cdiv(M, 128) * ntn;
-        for (int ks = 2; ks <= ks_max && nkt / ks >= 8; ++ks) {
+        for (int ks = 2; ks <= 8 && nkt / ks >= 8; ++ks) {
             const double per = (double)cdiv(nkt, ks);
             // + ~6 K-tiles worth of work per block for writing / re-reading the fp32 slab (3 measured against the
             // split-bf16 form's 64-row alternative on the short-K 1x1 layers)
-            // (round 4, whole-step sweeps of XV2_SLAB_COST - profiles/r04_gated_ab.md: the isolated-kernel fit of 3 / 4 K-tiles
+            // (round 4, whole-step sweeps of this charge - profiles/r04_gated_ab.md: the isolated-kernel fit of 3 / 4 K-tiles
             //  left out what the slab-sum LAUNCH costs the step; 9 / 12 measured 1 - 1.5 % faster on cfg2 fp32, cfg2 p16 and cfg3)
-            const double c = rounds(blocks128 * ks, cap128) * 128.0 * (per + slab_cost(math == XV2_MATH_F32X3 ? 9.0 : 6.0));
+            const double c = rounds(blocks128 * ks, cap128) * 128.0 * (per + (math == XV2_MATH_F32X3 ? 9.0 : 6.0));
             if (c < best * 0.95) {
                 best = c;
                 bm = 128;
@@ -349,15 +341,7 @@ bool f16x2_ready_pertap(IgemmParams& p) {
 // lived in scratch memory (3 extra VMEM round trips per stage) and the tap table was read with vector loads.  With both
 // gone: dec2 / dec3 116-GFLOP layers 0.592 -> 0.547 / 0.605 -> 0.553 ms, dec4 0.565 -> 0.483, l1.conv2 0.093 -> 0.077.
 // (Eight channels per thread with 16-byte plane stores - half the store instructions for the same bytes - measured 2-3 %
-// slower than the 4-channel / 8-byte form.)  XV2_HALO=0 restores the per-tap form (A/B runs).
-static bool halo_enabled() {
-    static const int v = [] { const char* e = getenv("XV2_HALO"); return e ? atoi(e) : 1; }();
-    return v != 0;
-}
-static bool presplit_enabled() {      // XV2_PRESPLIT=0: weights split in the kernel (A/B runs)
-    static const int v = [] { const char* e = getenv("XV2_PRESPLIT"); return e ? atoi(e) : 1; }();
-    return v != 0;
-}
+// slower than the 4-channel / 8-byte form.)
 // halo form of the bf16-storage kernel (both operands global -> LDS by DMA, no register path): exact, and measured NOT
 // faster than the per-tap form - cfg2 3x3 layers forward 550 -> 526, backward-data 598 -> 559 TFLOP/s (dec1 0.164 -> 0.203 ms,
 // dec2 / dec3 equal, l4.conv2 0.029 -> 0.026): that kernel has no split and no conversion to save, its producer is already
@@ -368,7 +352,7 @@ static bool halo_bf16_enabled() {
     return v != 0;
 }
 static bool halo_eligible(const IgemmParams& p, bool smallc, int math = XV2_MATH_F32X3) {
-    if (math == XV2_MATH_F32X3 ? !halo_enabled() : !halo_bf16_enabled()) return false;
+    if (math == XV2_MATH_BF16_STORE && !halo_bf16_enabled()) return false;
     if (smallc || p.math != math || p.ncls != 1 || p.s_in != 1 || p.Nout % 64 != 0) return false;
     const ClassInfo& c = p.cls[0];
     if (c.ntaps != 9 || c.tap0 != 0 || c.OHl != p.IH || c.OWl != p.IW || c.OHl % 4 != 0 || c.OWl % 32 != 0) return false;
@@ -445,7 +429,7 @@ int igemm_launch(IgemmParams& p, bool smallc, float* splitk_ws, hipStream_t stre
             if (f16x2_ready(p))
                 return bn == 128 ? launch_one<Form::F16X2_HALO, 128, 128>(p, stream) : launch_one<Form::F16X2_HALO, 128, 64>(p, stream);
             const void* x3 = nullptr;
-            if (presplit_enabled() && presplit_lookup(p.B, p.Nout, p.T, p.Ctot, &x3)) {
+            if (presplit_lookup(p.B, p.Nout, p.T, p.Ctot, &x3)) {
                 p.Bx3 = reinterpret_cast<const float*>(x3);
                 p.bytesBx3 = (unsigned)((size_t)p.Nout * p.T * p.Ctot * 6);
                 return bn == 128 ? launch_one<Form::F32X3_HALO_WX3, 128, 128>(p, stream) : launch_one<Form::F32X3_HALO_WX3, 128, 64>(p, stream);
@@ -463,7 +447,7 @@ int igemm_launch(IgemmParams& p, bool smallc, float* splitk_ws, hipStream_t stre
                 p.ksplit = nks;
                 const void* x3 = nullptr;
                 if (!halo16 && f16x2_ready(p)) {
-                } else if (!halo16 && presplit_enabled() && presplit_lookup(p.B, p.Nout, p.T, p.Ctot, &x3)) {
+                } else if (!halo16 && presplit_lookup(p.B, p.Nout, p.T, p.Ctot, &x3)) {
                     p.Bx3 = reinterpret_cast<const float*>(x3);
                     p.bytesBx3 = (unsigned)((size_t)p.Nout * p.T * p.Ctot * 6);
                 }
@@ -484,14 +468,13 @@ int igemm_launch(IgemmParams& p, bool smallc, float* splitk_ws, hipStream_t stre
         if (rc) return rc;
         const int M = p.cls[0].M;
         const dim3 rgrid((unsigned)cdiv(M, SPLITK_ROWS), (unsigned)cdiv(p.Nout, 256));
-        static const int rolled = [] { const char* e = getenv("XV2_SK_ALLROWS"); return (e && atoi(e) == 0) ? 0x100 : 0; }();
         if (p.math == XV2_MATH_BF16_STORE)
             hipLaunchKernelGGL(splitk_reduce_kernel<bf16_t>, rgrid, dim3(256), 0, stream, splitk_ws, p.ksplit, M, p.Nout,
-                               p.bias, (bf16_t*)p.Out0, p.ldo0, p.N0, (bf16_t*)p.Out1, p.ldo1, p.stats, p.accum | rolled,
+                               p.bias, (bf16_t*)p.Out0, p.ldo0, p.N0, (bf16_t*)p.Out1, p.ldo1, p.stats, p.accum,
                                p.ep_scale, p.ep_shift, (const bf16_t*)p.ep_res, p.ep_ldres, p.ep_act, (unsigned*)nullptr);
         else
             hipLaunchKernelGGL(splitk_reduce_kernel<float>, rgrid, dim3(256), 0, stream, splitk_ws, p.ksplit, M, p.Nout,
-                               p.bias, p.Out0, p.ldo0, p.N0, p.Out1, p.ldo1, p.stats, p.accum | rolled, p.ep_scale, p.ep_shift,
+                               p.bias, p.Out0, p.ldo0, p.N0, p.Out1, p.ldo1, p.stats, p.accum, p.ep_scale, p.ep_shift,
                                p.ep_res, p.ep_ldres, p.ep_act, p.amax_out);
         XV2_CHECK_LAUNCH();
         return XV2_OK;
@@ -814,10 +797,8 @@ extern "C" int xv2_conv_transpose2d_forward(const xv2_conv_desc* d, const void* 
     // the streaming kernel in its store loop (round 6: the pass of its own over the 268 MB of the 1024^2 level took 69 us per step)
     unsigned* slots = (d->math == XV2_MATH_F32X3 && ldy == d->C0) ? amax_ctx().out : nullptr;
     XV2_CHECK_ARG(!amax_ctx().out || slots, "conv_transpose2d: F16X2 maximum of a strided / non-fp32 output");
-    static const bool own_pass = [] { const char* e = getenv("XV2_AMAX_PASS"); return e && atoi(e) == 1; }();      // A/B runs: the round-5 form
-    int rc = thin_convT_forward(d, x, ldx, w_ihwo, y, ldy, own_pass ? nullptr : slots, (hipStream_t)stream);      // thin_conv.hip (records max |y| in its store loop)
+    const int rc = thin_convT_forward(d, x, ldx, w_ihwo, y, ldy, slots, (hipStream_t)stream);      // thin_conv.hip (records max |y| in its store loop)
     if (rc < 0) return dgrad_impl(d, (const float*)x, ldx, (const float*)w_ihwo, (float*)y, ldy, nullptr, 0, nullptr, (hipStream_t)stream);
-    if (rc == 0 && slots && own_pass) rc = xv2_tensor_amax_into(static_cast<const float*>(y), (int64_t)d->N * d->IH * d->IW * d->C0, slots, stream);
     return rc;
 }
 

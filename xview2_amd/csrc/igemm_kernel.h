@@ -1471,7 +1471,10 @@ __global__ void __launch_bounds__(256) splitk_reduce_kernel(const float* __restr
                 }
               }
             };
-            const bool rolled = (accum & 0x100) != 0;      // XV2_SK_ALLROWS=0 (A/B runs): the rolled loop
+            // bit 0x100 of `accum` selects the rolled loop for every slab count.  No launch sets it; the test stays because without it
+            // the register allocation of this kernel comes out differently (294 -> 296 VGPRs), and its code is the code that was measured.
+            // More than 8 slabs - only XV2_FORCE_TILE asks for them - take the rolled loop.
+            const bool rolled = (accum & 0x100) != 0;
             if (ksplit == 2 && !rolled) {
                 all_rows(std::integral_constant<int, 2>{});
             } else if (ksplit == 3 && !rolled) {

@@ -86,8 +86,7 @@ extern "C" int xv2_splat_tail_forward(const void* x, int N, int64_t hw, int C, i
     // gap_ready: `workspace` already holds the column-sum partials of x (xv2_bn_act_gap_forward: bn0's apply pass took them)
     int rc = gap_ready ? xv2_splat_gap_finish(N, hw, C, gap, workspace, stream) : xv2_splat_gap_forward(x, N, hw, C, gap, workspace, dtype, stream);
     if (rc) return rc;
-    const int fuse = xv2::splat_fuse_bits();
-    if ((fuse & 1) && parts >= 1 && N % parts == 0 && N / parts <= 64) {
+    if (parts >= 1 && N % parts == 0 && N / parts <= 64) {
         // fc1 + bn1 + ReLU and fc2 + rSoftMax as one launch each (norm_act.hip: the same arithmetic, two launches fewer per block)
         rc = xv2::splat_fc1_bn_launch(gap, w1, b1, N, C, inter, parts, train, gamma1, beta1, eps, momentum, running_mean, running_var,
                                       mean1, invstd1, scale1, shift1, h1, a1, (hipStream_t)stream);
@@ -114,16 +113,9 @@ extern "C" int xv2_splat_tail_backward(const void* x, const void* dout, int N, i
                                        const float* att, int train, int parts, float* datt, float* dlogits, float* da1,
                                        float* dh1, float* dgap, float* dw2, float* db2, float* dgamma1, float* dbeta1,
                                        float* dw1, float* db1, void* dx, float* workspace, int dtype, void* stream) {
-    int rc;
-    if (xv2::splat_fuse_bits() & 16) {      // datt's fold and rSoftMax's backward in one launch (bit-identical)
-        rc = xv2::splat_datt_rsoftmax_backward(x, att, dout, N, hw, C, datt, dlogits, workspace, dtype, stream);
-        if (rc) return rc;
-    } else {
-        rc = xv2_splat_apply_backward(x, att, dout, nullptr, N, hw, C, nullptr, datt, workspace, dtype, stream);
-        if (rc) return rc;
-        rc = xv2_rsoftmax_backward(att, datt, dlogits, N, C, stream);
-        if (rc) return rc;
-    }
+    // datt's fold and rSoftMax's backward in one launch (bit-identical to xv2_splat_apply_backward + xv2_rsoftmax_backward)
+    int rc = xv2::splat_datt_rsoftmax_backward(x, att, dout, N, hw, C, datt, dlogits, workspace, dtype, stream);
+    if (rc) return rc;
     rc = xv2_linear_backward(a1, w2, dlogits, da1, dw2, db2, N, inter, 2 * C, stream);
     if (rc) return rc;
     rc = xv2_bn_rows_backward(da1, a1, h1, mean1, invstd1, gamma1, N / parts, inter, parts, XV2_ACT_RELU, train, dh1, dgamma1,
@@ -152,9 +144,8 @@ extern "C" int xv2_conv_bn_act_forward_grouped(const xv2_conv_desc* d, int group
     xv2::AmaxGuard amax_guard;      // the context's sources serve every group, its `out` the apply pass
     const size_t es = dtype == XV2_BF16 ? 2 : 4;
     const int ctot = groups * d->Cout;
-    static const int one_grid = [] { const char* e = getenv("XV2_GROUPED_GRID"); return e ? atoi(e) : 1; }();
     int first = 0;
-    if (groups == 2 && one_grid) {
+    if (groups == 2) {
         // Both groups in ONE grid when group 0's convolution takes the small-grid kernel (sg_conv.hip, gridDim.y = 2): the statistics
         // partials then come out as rows of all 2 * Cout channels and one reduction serves both groups - per channel the same sums
         // in the same order as the per-group launches.  Otherwise `done` stays 0 and group 0 has run the ordinary way.
@@ -201,9 +192,8 @@ extern "C" int xv2_conv2d_backward_data_grouped(const xv2_conv_desc* d, int grou
     XV2_CHECK_ARG(d && groups >= 1 && w_ihwo && dy && dx0, "conv2d_backward_data_grouped: null argument");
     xv2::AmaxGuard amax_guard;      // dy's maximum serves every group
     const size_t es = dtype == XV2_BF16 ? 2 : 4;
-    static const int one_grid = [] { const char* e = getenv("XV2_GROUPED_GRID"); return e ? atoi(e) : 1; }();
     int first = 0;
-    if (groups == 2 && one_grid) {      // (see xv2_conv_bn_act_forward_grouped)
+    if (groups == 2) {      // (see xv2_conv_bn_act_forward_grouped)
         xv2::SgGroupCtx& gc = xv2::sg_group_ctx();
         gc.active = 1; gc.w1 = w_ihwo[1]; gc.done = 0;
         int rc = xv2_conv2d_backward_data_acc(d, dy, lddy, w_ihwo[0], dx0, lddx0, nullptr, 0, accumulate, workspace, stream);

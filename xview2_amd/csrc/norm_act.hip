@@ -14,17 +14,6 @@
 
 namespace xv2 {
 
-// experiment hook (XV2_BN_BLOCKS): cap on the grid of the streaming BatchNorm kernels - smaller grids leave wave slots
-// to weight-gradient kernels co-scheduled from the side stream
-static int bn_blocks(int dflt) {
-    static int v = -2;
-    if (v == -2) {
-        const char* e = getenv("XV2_BN_BLOCKS");
-        v = e ? atoi(e) : -1;
-    }
-    return v > 0 ? v : dflt;
-}
-
 // ---------------------------------------------------------------------------------------------
 // column partials: for every chunk of `rpb` rows, part[chunk][C][2] = (sum f0, sum f1) per channel.
 // F(row, c4 or c, vec) returns the two quantities to accumulate.
@@ -49,9 +38,9 @@ static ChunkGeom chunk_geom(int64_t npix, int C, int W = 4) {
     }
     if (g.cgw) g.groups = C / g.cgw;
     const int64_t rows_per_pass = g.cgw ? 256 / (g.cgw / W) : 4;
-    // (bf16 tensors - W = 8 channels per 16-byte lane - are half the bytes: half the blocks; whole-step sweeps of XV2_BN_BLOCKS,
+    // (bf16 tensors - W = 8 channels per 16-byte lane - are half the bytes: half the blocks; whole-step sweeps of the block cap,
     //  cfg3 15.75 -> 15.66 ms, cfg2 --precision 16 12.53 -> 12.44 ms; fp32 tensors are indifferent between 1024 and 8192)
-    int64_t rpb = cdiv(npix * g.groups, bn_blocks(W == 8 ? 1024 : 2048));
+    int64_t rpb = cdiv(npix * g.groups, W == 8 ? 1024 : 2048);
     rpb = cdiv(rpb, rows_per_pass) * rows_per_pass;
     if (rpb < rows_per_pass * 8) rpb = rows_per_pass * 8;
     g.rpb = (int)rpb;
@@ -173,14 +162,12 @@ struct ColOp {
     }
 };
 
-// XV2_BN_REVERSE (A/B runs): bit 0 = the backward apply, bit 1 = the forward apply, bit 2 = the backward column sums walk
-// their tensors last-to-first
+// walk order of the streaming kernels (their `rev` argument): the backward apply and the forward apply walk their tensors
+// last-to-first, the column sums first-to-last.  `rev` stays a run-time argument of the kernels: the launch sites pass
+// these constants, and the kernels' code is the code that was measured.
 // (rounds 3 - 5 could fold the chunk / tile partials inside the producing launch - XV2_BN_FOLD, device-scope tickets; removed in
 //  round 6: +0.65 ms per cfg2 step once fenced correctly)
-static int bn_reverse(int bit) {
-    static const int v = [] { const char* e = getenv("XV2_BN_REVERSE"); return e ? atoi(e) : 3; }();
-    return (v >> bit) & 1;
-}
+constexpr int BN_REV_BWD_APPLY = 1, BN_REV_FWD_APPLY = 1, BN_REV_COLUMN_SUMS = 0;
 
 template <int MODE, typename T, int COUT = 0>
 __global__ void __launch_bounds__(256) column_partials_kernel(ColOp<MODE, T, COUT> op, int64_t npix, int C, int rpb, int cgw,
@@ -503,12 +490,10 @@ template <typename T>
 static int reduce_stats(const T* partial, int64_t tiles, int C, double* sums, double* scratch, hipStream_t st,
                         float* f0 = nullptr, float* f1 = nullptr, const BnFinalize* fin = nullptr) {
     int S = (int)std::min<int64_t>(XV2_BN_SCRATCH_ROWS, cdiv(tiles, 16));
-    static const int force_s1 = [] { const char* e = getenv("XV2_STATS_S1"); return e ? atoi(e) : 0; }();      // (race hunting: no ticket hand-off)
-    if (S < 1 || force_s1) S = 1;
+    if (S < 1) S = 1;
     const int groups = (int)cdiv(C, 32);
     XV2_CHECK_ARG(groups <= 4096, "reduce_stats: C=%d too large", C);
-    static const int one_phase = [] { const char* e = getenv("XV2_STATS_1PHASE"); return e ? atoi(e) : 1; }();      // (A/B runs: 0 = always the ticket form)
-    if (one_phase && tiles <= RS1_MAX_TILES && !force_s1) {
+    if (tiles <= RS1_MAX_TILES) {
         BnFinalize none1;
         memset(&none1, 0, sizeof(none1));
         hipLaunchKernelGGL(reduce_stats_1phase_kernel<T>, dim3((unsigned)groups), dim3(1024), 0, st, partial, tiles, C, sums, f0, f1,
@@ -1030,7 +1015,7 @@ __global__ void __launch_bounds__(256) bn_rows_bwd_kernel(const float* __restric
 
 static inline int ew_grid(int64_t total) {
     int64_t b = cdiv(total, 256);
-    if (b > bn_blocks(256 * 16)) b = bn_blocks(256 * 16);
+    if (b > 256 * 16) b = 256 * 16;
     if (b < 1) b = 1;
     return (int)b;
 }
@@ -1075,7 +1060,7 @@ static int column_sums(const ColOp<MODE, T>& op, int64_t npix, int C, double* su
     double* dpart = reinterpret_cast<double*>(workspace);
     double* scratch = reinterpret_cast<double*>(reinterpret_cast<char*>(workspace) + part);
     hipLaunchKernelGGL((column_partials_kernel<MODE, T>), dim3((unsigned)g.chunks, g.groups), dim3(256), 0, st, op, npix,
-                       C, g.rpb, g.cgw, dpart, MODE == 1 ? bn_reverse(2) : 0);
+                       C, g.rpb, g.cgw, dpart, BN_REV_COLUMN_SUMS);
     XV2_CHECK_LAUNCH();
     return reduce_stats<double>(dpart, g.chunks, C, sums, scratch, st, f0, f1);
 }
@@ -1142,7 +1127,7 @@ static int bn_act_forward_impl(const T* y, int ldy, const float* scale, const fl
     const int grid = ew_grid(npix * (vec ? C / W : C));
     if (vec)
         hipLaunchKernelGGL((bn_act_fwd_kernel<true, T>), dim3(grid), dim3(256), 0, (hipStream_t)stream, y, ldy, scale,
-                           shift, residual, ldr, act, z, ldz, npix, C, zmask, bn_reverse(1), amax);
+                           shift, residual, ldr, act, z, ldz, npix, C, zmask, BN_REV_FWD_APPLY, amax);
     else
         hipLaunchKernelGGL((bn_act_fwd_kernel<false, T>), dim3(grid), dim3(256), 0, (hipStream_t)stream, y, ldy, scale,
                            shift, residual, ldr, act, z, ldz, npix, C, (uint8_t*)nullptr, 0, amax);
@@ -1227,11 +1212,11 @@ static int bn_bwd_apply_impl(const T* dz, int lddz, const T* z, int ldz, int zbi
     const ChunkGeom cg = chunk_geom(npix, C, W);
     if (vecw && cg.cgw) {
         const int rpp = 256 / (cg.cgw / W);
-        int64_t rpb = cdiv(npix * cg.groups, bn_blocks(sizeof(T) == 2 ? 2048 : 4096));
+        int64_t rpb = cdiv(npix * cg.groups, sizeof(T) == 2 ? 2048 : 4096);
         rpb = std::max<int64_t>(cdiv(rpb, rpp) * rpp, rpp * 4);
         hipLaunchKernelGGL(bn_act_bwd_rows_kernel<T>, dim3((unsigned)cdiv(npix, rpb), cg.groups), dim3(256), 0,
                            (hipStream_t)stream, dz, lddz, z, ldz, y, ldy, mean, invstd, gamma, scale, shift, sums2,
-                           count, act, train, dy, lddy, dres, lddres, npix, cg.cgw, (int)rpb, zbits, C / 4, bn_reverse(0), amax);
+                           count, act, train, dy, lddy, dres, lddres, npix, cg.cgw, (int)rpb, zbits, C / 4, BN_REV_BWD_APPLY, amax);
         XV2_CHECK_LAUNCH();
         return XV2_OK;
     }
@@ -1301,7 +1286,7 @@ static int bn_act_head_forward_impl(const T* y, int ldy, const float* scale, con
     prof_begin(head_prof_id(2), 0.0, 0.0, st);
 #define LAUNCH_BHF(CO)                                                                                                     \
     hipLaunchKernelGGL((bn_act_head_fwd_kernel<CO, T>), dim3(grid), dim3(256), 0, st, y, ldy, scale, shift, act, npix, hw, C, w, \
-                       bias, logits, nchw_out, head_hw_div(npix, hw), L, bn_reverse(1))
+                       bias, logits, nchw_out, head_hw_div(npix, hw), L, BN_REV_FWD_APPLY)
     switch (Cout) {
         case 1: LAUNCH_BHF(1); break;
         case 2: LAUNCH_BHF(2); break;
@@ -1351,7 +1336,7 @@ static int bn_act_head_backward_impl(const float* dlogits, int nchw, int64_t hw,
     // pass 1: (sum g, sum g * xhat) per channel, in the unfused pass's row chunks; then its fold
     prof_begin(head_prof_id(3), 0.0, 0.0, st);
     hipLaunchKernelGGL((column_partials_kernel<2, T, COUT>), dim3((unsigned)g.chunks, 1), dim3(256), 0, st, op, npix, C, g.rpb, g.cgw,
-                       dpart, bn_reverse(2));
+                       dpart, BN_REV_COLUMN_SUMS);
     prof_end(st);
     XV2_CHECK_LAUNCH();
     int rc = reduce_stats<double>(dpart, g.chunks, C, sums2, scratch, st, dbeta, dgamma);

@@ -508,11 +508,6 @@ __device__ __forceinline__ void linear_bwd_dx_block(const float* __restrict__ w,
         dx[(size_t)n * Cin + c] = a;
     }
 }
-__global__ void __launch_bounds__(256) linear_bwd_dx_kernel(const float* __restrict__ w, const float* __restrict__ dy,
-                                                             float* __restrict__ dx, int N, int Cin, int Cout) {
-    __shared__ float sh[256];
-    linear_bwd_dx_block(w, dy, dx, Cin, Cout, blockIdx.x, blockIdx.y, sh);
-}
 __device__ __forceinline__ void linear_bwd_dw_block(const float* __restrict__ x, const float* __restrict__ dy,
                                                     float* __restrict__ dw, float* __restrict__ db, int N, int Cin, int Cout, int bx) {
     const int i = bx * blockDim.x + threadIdx.x;
@@ -531,9 +526,9 @@ __global__ void linear_bwd_dw_kernel(const float* __restrict__ x, const float* _
                                      float* __restrict__ dw, float* __restrict__ db, int N, int Cin, int Cout) {
     linear_bwd_dw_block(x, dy, dw, db, N, Cin, Cout, blockIdx.x);
 }
-// both products of a dense layer's backward as ONE launch (problem-indexed grid: the first nbx * N blocks are the blocks of
-// linear_bwd_dx_kernel, the rest those of linear_bwd_dw_kernel - the same block code, bit-identical results, one launch less per
-// dense layer: 264 per resnest200 step)
+// both products of a dense layer's backward as ONE launch (problem-indexed grid: the first nbx * N blocks run
+// linear_bwd_dx_block, the rest are the blocks of linear_bwd_dw_kernel - the same block code as a launch each, bit-identical
+// results, one launch less per dense layer: 264 per resnest200 step)
 __global__ void __launch_bounds__(256) linear_bwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                           const float* __restrict__ dy, float* __restrict__ dx,
                                                           float* __restrict__ dw, float* __restrict__ db, int N, int Cin, int Cout,
@@ -825,17 +820,12 @@ extern "C" int xv2_splat_gap_forward(const void* x, int N, int64_t hw, int C, fl
     XV2_CHECK_LAUNCH();
     return XV2_OK;
 }
-// switches for A/B runs (XV2_SPLAT_FUSE, default 5): bit 0 = fc1 + bn1 and fc2 + rSoftMax as one launch each, bit 2 = the GAP's column
-// sums taken by bn0's apply pass.  (Measured and removed, round 6: fc2 + rSoftMax inside the apply launch - every block deriving the
-// attention weights of its own 64 channels first - bit-identical and +0.42 ms per resnest50 encoder forward: a latency-bound
-// prologue in front of 2048 streaming blocks costs more than the 5 us launch it replaces.)
-namespace xv2 {
-int splat_fuse_bits() {
-    static const int v = [] { const char* e = getenv("XV2_SPLAT_FUSE"); return e ? atoi(e) : 29; }();
-    return v;
-}
-}  // namespace xv2
-extern "C" int xv2_bn_act_gap_supported(int C) { return (splat_fuse_bits() & 4) && splat_vec_ok(C) ? 1 : 0; }
+// the fused launches of the split-attention tail (fc1 + bn1 and fc2 + rSoftMax as one launch each, the GAP's column sums taken
+// by bn0's apply pass, the backward's fused folds) run wherever their shape conditions hold.  (Measured and removed, round 6:
+// fc2 + rSoftMax inside the apply launch - every block deriving the attention weights of its own 64 channels first -
+// bit-identical and +0.42 ms per resnest50 encoder forward: a latency-bound prologue in front of 2048 streaming blocks costs
+// more than the 5 us launch it replaces.)
+extern "C" int xv2_bn_act_gap_supported(int C) { return splat_vec_ok(C) ? 1 : 0; }
 extern "C" int xv2_bn_act_gap_forward(const void* y, const float* scale, const float* shift, int act, void* z, int N, int64_t hw,
                                       int C, float* workspace, int dtype, void* stream) {
     XV2_CHECK_ARG(y && scale && shift && z && workspace && N >= 1 && hw >= 1, "bn_act_gap_forward: null argument");
@@ -898,7 +888,7 @@ extern "C" int xv2_splat_apply_backward(const void* x, const float* att, const v
 }
 namespace xv2 {
 // the first two steps of the split-attention tail's backward as two launches instead of three: datt (column sums of dout * x,
-// folded) AND rSoftMax's backward in the fold launch (XV2_SPLAT_FUSE bit 4; layer_entry.cpp xv2_splat_tail_backward)
+// folded) AND rSoftMax's backward in the fold launch (layer_entry.cpp xv2_splat_tail_backward)
 int splat_datt_rsoftmax_backward(const void* x, const float* att, const void* dout, int N, int64_t hw, int C, float* datt,
                                  float* dlogits, float* workspace, int dtype, void* stream) {
     XV2_CHECK_ARG(C % 4 == 0 && splat_vec_ok(C), "splat_apply: unsupported channel count %d", C);
@@ -925,16 +915,11 @@ extern "C" int xv2_linear_forward(const float* x, const float* w, const float* b
 extern "C" int xv2_linear_backward(const float* x, const float* w, const float* dy, float* dx, float* dw, float* db,
                                    int N, int Cin, int Cout, void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    if (dx && (splat_fuse_bits() & 8)) {      // both products in one launch (XV2_SPLAT_FUSE bit 3)
+    if (dx) {      // both products in one launch
         const int nbx = (int)cdiv(Cin, LB_COLS), nbw = (int)cdiv(Cout * (Cin + 1), 256);
         hipLaunchKernelGGL(linear_bwd_kernel, dim3((unsigned)(nbx * N + nbw)), dim3(256), 0, st, x, w, dy, dx, dw, db, N, Cin, Cout, nbx);
         XV2_CHECK_LAUNCH();
         return XV2_OK;
-    }
-    if (dx) {
-        hipLaunchKernelGGL(linear_bwd_dx_kernel, dim3((unsigned)cdiv(Cin, LB_COLS), N), dim3(256), 0, st, w, dy, dx, N, Cin,
-                           Cout);
-        XV2_CHECK_LAUNCH();
     }
     hipLaunchKernelGGL(linear_bwd_dw_kernel, dim3((unsigned)cdiv(Cout * (Cin + 1), 256)), dim3(256), 0, st, x, dy, dw,
                        db, N, Cin, Cout);

@@ -295,13 +295,8 @@ __global__ void __launch_bounds__(256, 2) stem7x7_wgrad_kernel(const StemWgradPa
     }
 }
 
-static bool stem_enabled() {      // XV2_STEM7=0: the implicit-GEMM kernel (A/B runs)
-    static const int v = [] { const char* e = getenv("XV2_STEM7"); return e ? atoi(e) : 1; }();
-    return v != 0;
-}
-
 bool stem7x7_eligible(const IgemmParams& p, bool smallc) {
-    if (!stem_enabled() || !smallc || p.ncls != 1 || p.Nout != 64 || p.N0 != 64 || p.T != 49 || p.s_in != 2) return false;
+    if (!smallc || p.ncls != 1 || p.Nout != 64 || p.N0 != 64 || p.T != 49 || p.s_in != 2) return false;
     if (p.math == XV2_MATH_BF16 || p.accum || p.ep_res || (p.ep_scale && p.stats) || p.Out1 || p.A1 || p.ldA0 != 4) return false;
     const ClassInfo& c = p.cls[0];
     if (c.ntaps != 49 || c.tap0 != 0 || c.os0 != 0 || p.osW != 1 || p.osH != c.OWl || p.osN != c.OHl * c.OWl) return false;
@@ -348,8 +343,7 @@ int stem7x7_launch(const IgemmParams& p, hipStream_t stream) {
 
 // plan: slabs the weight-gradient kernel writes for this geometry (0 = not this kernel's layer)
 int stem7x7_wgrad_slabs(const xv2_conv_desc* d) {
-    static const int on = [] { const char* e = getenv("XV2_STEM7W"); return e ? atoi(e) : 1; }();
-    if (!on || !stem_enabled() || d->C0 != 4 || d->C1 != 0 || d->Cout != 64 || d->KH != 7 || d->KW != 7 || d->stride != 2 ||
+    if (d->C0 != 4 || d->C1 != 0 || d->Cout != 64 || d->KH != 7 || d->KW != 7 || d->stride != 2 ||
         d->pad != 3 || d->dil != 1 || d->math == XV2_MATH_BF16_STORE || d->math == XV2_MATH_BF16)
         return 0;
     if (d->OH % S_PH != 0 || d->OW % S_PW != 0 || d->OH * 2 != d->IH || d->OW * 2 != d->IW) return 0;

@@ -347,11 +347,6 @@ __global__ void __launch_bounds__(WAVES * 64, (HS || PF == 2) ? 2 : 1) thin1x1_k
         if (p.amax_out) amax_record_wave(p.amax_out, omax, blockIdx.x * WAVES + wave);
 }
 
-static bool thin_enabled() {      // XV2_THIN=0: these layers stay on the tiled implicit-GEMM kernel (A/B runs)
-    static const bool on = [] { const char* e = getenv("XV2_THIN"); return !(e && atoi(e) == 0); }();
-    return on;
-}
-
 template <int K, int N, bool HS, int WAVES, int SUBS, int MODE = 0, int PF = 3>
 static int thin_launch_one(const ThinParams& q, const char* name, double flops, double abytes, hipStream_t stream) {
     constexpr int WPT = 4 / SUBS;
@@ -376,7 +371,7 @@ static bool thin_shape(int K, int N, int math) {
 }
 
 bool thin1x1_eligible(const IgemmParams& p, bool smallc) {
-    if (!thin_enabled() || smallc || (p.math != XV2_MATH_F32X3 && p.math != XV2_MATH_BF16_STORE)) return false;
+    if (smallc || (p.math != XV2_MATH_F32X3 && p.math != XV2_MATH_BF16_STORE)) return false;
     if (p.ncls != 1 || p.T != 1 || p.s_in != 1 || p.C1 != 0 || p.A1 || p.Out1 || p.N0 != p.Nout) return false;
     if (p.bias || p.ep_scale || p.ksplit != 1) return false;
     const ClassInfo& c = p.cls[0];
@@ -409,12 +404,10 @@ int thin1x1_launch(const IgemmParams& p, hipStream_t stream) {
     const bool hs = p.math == XV2_MATH_BF16_STORE;
     const double es = hs ? 2.0 : 4.0;
     const double flops = 2.0 * q.M * (double)N * K, abytes = es * ((double)q.M * (K + N) + (double)K * N);
-    // bf16 tensors: two waves per tile (XV2_THIN_SUBS=4: one wave per tile, A/B runs)
-    static const bool wide = [] { const char* e = getenv("XV2_THIN_SUBS"); return !(e && atoi(e) == 4); }();
+    // bf16 tensors: two waves per tile
 #define XV2_THIN_CASE(KK, NN)                                                                                        \
     if (K == KK && N == NN)                                                                                          \
-        return hs ? (wide ? thin_launch_one<KK, NN, true, 2, 2>(q, "thin1x1_kernel<" #KK "," #NN ",bf16hbm>", flops, abytes, stream)  \
-                          : thin_launch_one<KK, NN, true, 2, 4>(q, "thin1x1_kernel<" #KK "," #NN ",bf16hbm>", flops, abytes, stream)) \
+        return hs ? thin_launch_one<KK, NN, true, 2, 2>(q, "thin1x1_kernel<" #KK "," #NN ",bf16hbm>", flops, abytes, stream) \
                   : h2 ? thin_launch_one<KK, NN, false, 4, 4, 0, 2>(q, "thin1x1_kernel<" #KK "," #NN ",f16x2>", flops, abytes, stream) \
                        : thin_launch_one<KK, NN, false, 4, 4>(q, "thin1x1_kernel<" #KK "," #NN ",f32x3>", flops, abytes, stream);
     XV2_THIN_CASE(64, 64)
@@ -431,8 +424,7 @@ int thin1x1_launch(const IgemmParams& p, hipStream_t stream) {
 // 402 MB for 8.6 GFLOP each - the tiled kernel ran them at 0.18 / 0.14 ms, 2 - 3x their HBM floor.  `d` = the equivalent
 // 2x2 / stride-2 convolution (C0 = 32 big-grid channels, Cout = 64 small-grid channels).  Return -1: not this kernel's shape.
 static bool thin_ct_shape(const xv2_conv_desc* d, int ld_small, int ld_big, const void* a, const void* b, const void* c) {
-    static const bool on = [] { const char* e = getenv("XV2_THIN_CT"); return !(e && atoi(e) == 0); }();
-    if (!on || !thin_enabled() || (d->math != XV2_MATH_F32X3 && d->math != XV2_MATH_BF16_STORE)) return false;
+    if ((d->math != XV2_MATH_F32X3 && d->math != XV2_MATH_BF16_STORE)) return false;
     if (d->C0 != 32 || d->C1 != 0 || d->Cout != 64 || d->KH != 2 || d->KW != 2 || d->stride != 2 || d->pad != 0 || d->dil != 1) return false;
     if (d->OW % 32 != 0 || d->IH != 2 * d->OH || d->IW != 2 * d->OW || (long long)d->N * d->OH * d->OW < 65536) return false;
     const long long es = d->math == XV2_MATH_BF16_STORE ? 2 : 4;
@@ -462,21 +454,17 @@ int thin_convT_backward_data(const xv2_conv_desc* d, const void* dy, int lddy, c
                              int accumulate, hipStream_t stream) {
     if (!thin_ct_shape(d, lddx, lddy, dy, w_ohwi, dx)) return -1;
     // (fp32 tensors: the K = 128 gather form needs 338 + 82 registers and ran at 0.283 ms against 0.14 ms of the tiled kernel -
-    //  measured, profiles/r04_gated_ab.md; bf16 storage only, XV2_THIN_CT=2 forces it for A/B runs)
-    static const bool force = [] { const char* e = getenv("XV2_THIN_CT"); return e && atoi(e) == 2; }();
-    if (d->math != XV2_MATH_BF16_STORE && !force) return -1;
+    //  measured, profiles/r04_gated_ab.md; bf16 storage only)
+    if (d->math != XV2_MATH_BF16_STORE) return -1;
     ThinParams q;
     q.amaxA = q.amaxB = nullptr;
     q.amax_out = nullptr;
     q.A = dy; q.B = w_ohwi; q.Out = dx; q.stats = nullptr;
     q.M = d->N * d->OH * d->OW; q.ldA = lddy; q.ldo = lddx; q.accum = accumulate & 1; q.W = d->OW;
     q.tiles = (int)cdiv(q.M, 128);
-    const bool hs = d->math == XV2_MATH_BF16_STORE;
-    const double es = hs ? 2.0 : 4.0;
-    q.bytesA = (unsigned)((double)d->N * d->IH * d->IW * lddy * es);
-    const double flops = 2.0 * q.M * 128.0 * 64.0, abytes = es * ((double)q.M * (64 + 128) + 64.0 * 128);
-    return hs ? thin_launch_one<128, 64, true, 2, 2, 2>(q, "thin_convT_bwd<32,64,bf16hbm>", flops, abytes, stream)
-              : thin_launch_one<128, 64, false, 4, 4, 2>(q, "thin_convT_bwd<32,64,f32x3>", flops, abytes, stream);
+    q.bytesA = (unsigned)((double)d->N * d->IH * d->IW * lddy * 2.0);
+    const double flops = 2.0 * q.M * 128.0 * 64.0, abytes = 2.0 * ((double)q.M * (64 + 128) + 64.0 * 128);
+    return thin_launch_one<128, 64, true, 2, 2, 2>(q, "thin_convT_bwd<32,64,bf16hbm>", flops, abytes, stream);
 }
 
 }  // namespace xv2

@@ -369,8 +369,7 @@ static int wgrad_impl(const xv2_conv_desc* d_in, const float* x0, int ldx0, cons
     p.M = d->N * d->OH * d->OW;
     p.T = d->KH * d->KW;
     p.ktiles = pl.ktiles; p.kt_per_split = pl.kt_per;
-    static const int xcd_on = [] { const char* e = getenv("XV2_WGRAD_XCD"); return e ? atoi(e) : 1; }();      // (A/B runs: 0 = dispatch order)
-    p.xcd_order = xcd_on;
+    p.xcd_order = 1;
     p.tiles_n = pl.smallc ? (int)cdiv(p.T * 4, pl.bn) : p.Ctot / pl.bn;
     const size_t total = (size_t)d->Cout * p.T * p.Ctot;
     {

@@ -52,7 +52,7 @@ struct WgradParams {
     const unsigned* amaxX0;
     const unsigned* amaxX1;
     const unsigned* amaxDY;
-    int xcd_order;      // 1: XCD-aware block order (wgrad_block)
+    int xcd_order;      // 1: XCD-aware block order (wgrad_block); always 1 - kept as a field so that the kernels' code stays as measured
     WTap taps[52];
 };
 

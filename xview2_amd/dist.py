@@ -20,16 +20,9 @@ from . import nn as xnn
 
 
 def nccl_options():
-    """RCCL kernels on a high-priority stream (XV2_NCCL_HIGH_PRIO=1): experiment hook for the latency of the ~126
-    small SyncBatchNorm collectives per step"""
-    if os.environ.get("XV2_NCCL_HIGH_PRIO", "0") != "1":
-        return None
-    try:
-        opts = dist.ProcessGroupNCCL.Options()
-        opts.is_high_priority_stream = True
-        return opts
-    except Exception:  # noqa: BLE001
-        return None
+    """process-group options for the RCCL backend: none (bench.py asks before it creates its own group).  RCCL kernels on a
+    high-priority stream measured 37.7 -> 64.5 ms per step"""
+    return None
 
 
 def init_from_env(backend=None):
@@ -44,11 +37,7 @@ def init_from_env(backend=None):
             backend = "nccl" if torch.cuda.is_available() else "gloo"
         if backend == "nccl":
             torch.cuda.set_device(local)
-        opts = nccl_options() if backend == "nccl" else None
-        if opts is not None:
-            dist.init_process_group(backend, rank=rank, world_size=world, pg_options=opts)
-        else:
-            dist.init_process_group(backend, rank=rank, world_size=world)
+        dist.init_process_group(backend, rank=rank, world_size=world)
     return rank, local, world
 
 

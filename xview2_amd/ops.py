@@ -143,7 +143,6 @@ _desc_cache = {}
 # in-place update bumps `_version`; FlatAdamW (whose kernel torch cannot see) bumps WEIGHT_EPOCH and then refreshes
 # every cached layout with ONE table-driven launch (repack_all) instead of one small launch per layer per step.
 WEIGHT_EPOCH = 0
-PACK_CACHE = os.environ.get("XV2_PACK_CACHE", "1") != "0"
 _packs = {}
 _pack_table = None
 _repack_tick = 0
@@ -157,7 +156,6 @@ class _PackEntry:
     __slots__ = ("w", "version", "epoch", "ohwi", "ihwo", "geom", "tick", "owner", "dtype", "x3", "x2", "amax", "amax_reg")
 
 
-PRESPLIT = os.environ.get("XV2_PRESPLIT", "1") != "0"
 # F16X2 (include/xv2.h): fp32 tensors, operands as two scaled fp16 planes - three matrix instructions per product instead of six
 # - for every launch whose operand maxima are known.  A tensor's maximum is recorded by the kernel that writes it (BatchNorm apply,
 # forward and backward) into 64 slots that travel with the tensor as the attribute _xv2_amax; weights get theirs when their planes
@@ -278,7 +276,7 @@ def _presplit_geoms(e, planes=3):
     (F16X2: the halo form and the small-grid kernel sg_conv.hip, which also takes the 1x1 layers: xv2_presplit_f16_supported)"""
     Cout, Cin, T, cin_pad = e.geom
     out = []
-    if not PRESPLIT or e.dtype != XV2_F32 or cin_pad == 4 or MATH_MODE != MATH_F32X3:
+    if e.dtype != XV2_F32 or cin_pad == 4 or MATH_MODE != MATH_F32X3:
         return out      # (planes made under F32X3 stay registered if the mode is switched later: harmless, just unused)
     fn = "xv2_presplit_supported" if planes == 3 else "xv2_presplit_f16_supported"
     if e.ohwi is not None and query(fn, Cout, T, cin_pad) == 1:
@@ -403,11 +401,6 @@ def _pack(w_oihw, cin_pad, want_ohwi, want_ihwo, half=False):
     Cout, Cin, KH, KW = w_oihw.shape
     pdt = torch.bfloat16 if (half and cin_pad != 4) else torch.float32
     code = XV2_BF16 if pdt == torch.bfloat16 else XV2_F32
-    if not PACK_CACHE:
-        ohwi = _act((Cout, KH * KW, cin_pad), w_oihw, pdt) if want_ohwi else None
-        ihwo = _act((cin_pad, KH * KW, Cout), w_oihw, pdt) if want_ihwo else None
-        call("xv2_pack_weight", w_oihw, Cout, Cin, KH, KW, cin_pad, ohwi, ihwo, code)
-        return ohwi, ihwo
     key = (w_oihw.data_ptr(), Cout, Cin, KH, KW, cin_pad, code)
     e = _packs.get(key)
     base = w_oihw._base if w_oihw._base is not None else w_oihw
@@ -469,7 +462,7 @@ def repack_all():
     """refresh every cached layout in one launch on the current stream (call right after weights_changed())"""
     global _pack_table
     global _repack_tick
-    if not _packs or not PACK_CACHE:
+    if not _packs:
         return
     _drop_dead_packs()
     stale = [k for k, e in _packs.items() if e.tick <= _repack_tick]     # not touched since the last refresh
@@ -547,9 +540,6 @@ def _stats_scratch(C, device):
     return t
 
 
-STEM_BAND = os.environ.get("XV2_STEM_BAND", "1") != "0"      # --precision 16: RGB stem on the 32-channel bf16 kernel (xv2_pad_band)
-
-
 def _conv_forward(x0, x1, weight, g, bias=None, want_stats=False, ihwo_out=None, bn=None, fused=None, amax_in=None, amax_out=None):
     """-> y [N,OH,OW,Cout], sums (double [Cout,2]) or None.
     If `ihwo_out` is a list, the backward-data weight packs are produced by the same repack launch and appended to it (one
@@ -576,7 +566,7 @@ def _conv_forward(x0, x1, weight, g, bias=None, want_stats=False, ihwo_out=None,
         bn_stats_changed()
     stats_ok = True        # False: the M tiles do not split evenly over the S parts -> statistics taken from y afterwards
     band_w = None
-    if (rgb and STEM_BAND and G == 1 and ihwo_out is None and 5 <= g.kw <= 8 and
+    if (rgb and G == 1 and ihwo_out is None and 5 <= g.kw <= 8 and
             g.stride == 2 and g.dil == 1 and half):
         # RGB stem as a band convolution (xv2_pad_band): KH taps x 32 "channels" (8 pixels x 4) on the 32-channel bf16 kernel
         # instead of the exact-fp32 gather kernel - under --precision 16 only: for fp32 tensors the split-bf16 form of the
@@ -681,7 +671,7 @@ def _conv_bn_act_train(x0, x1, weight, g, bn, residual, act, ihwo_out, want_mask
     half = (STORAGE == torch.bfloat16) if rgb else x0.dtype == torch.bfloat16
     if x1 is not None and x1.dtype != x0.dtype:
         raise RuntimeError("convolution sources of different element types (%s, %s)" % (x0.dtype, x1.dtype))
-    if rgb and STEM_BAND and ihwo_out is None and 5 <= g.kw <= 8 and g.stride == 2 and g.dil == 1 and half:
+    if rgb and ihwo_out is None and 5 <= g.kw <= 8 and g.stride == 2 and g.dil == 1 and half:
         return None      # the RGB stem runs as a band convolution (_conv_forward)
     G = g.groups
     if head is not None and (G > 1 or residual is not None or rgb):
@@ -808,10 +798,7 @@ def _conv_backward_data(dy, weight, g, in_shape, C0t, C1t, ihwo_packs=None, add_
 # Weight gradients are needed only at the optimizer step (or by the gradient all-reduce), so their kernels can run
 # on a side stream concurrently with the backward-data / BatchNorm chain: the tails of the many ~100 us encoder
 # launches overlap instead of serialising.  join_wgrad_stream() is called before anything consumes the gradients.
-ASYNC_WGRAD = os.environ.get("XV2_ASYNC_WGRAD", "1") != "0"
-# which weight gradients go to the side stream: "all" (default) | "3x3" (only multi-tap layers; the 1x1 layers run on the
-# compute stream right after their backward-data - VERDICT r02 item 6 A/B) | "1x1"
-WGRAD_SIDE = os.environ.get("XV2_WGRAD_SIDE", "all")
+ASYNC_WGRAD = True      # (wgrad_on_compute_stream switches it off for its block)
 _wgrad_stream = None
 
 
@@ -831,23 +818,12 @@ class wgrad_on_compute_stream:
         return False
 
 
-def _priority_stream(prio):
-    """experiment hook (XV2_WGRAD_PRIORITY): a HIP stream at an explicit queue priority (1 = lowest, -1 = highest).
-    Measured: no gain on one GPU, and at the LOWEST priority the step with RCCL collectives in it (SyncBatchNorm,
-    gradient buckets) slows from 38 to 58 ms - so the default is an ordinary stream."""
-    import ctypes
-    hip = ctypes.CDLL("libamdhip64.so")
-    h = ctypes.c_void_p()
-    if hip.hipStreamCreateWithPriority(ctypes.byref(h), 1, int(prio)) != 0 or not h.value:   # 1 = hipStreamNonBlocking
-        return torch.cuda.Stream()
-    return torch.cuda.ExternalStream(h.value)
-
-
 def _side_stream():
+    """an ordinary stream (an explicit queue priority measured no gain on one GPU and, at the lowest, 38 -> 58 ms per step
+    with RCCL collectives in it: DESIGN.md section 4)"""
     global _wgrad_stream
     if _wgrad_stream is None:
-        prio = os.environ.get("XV2_WGRAD_PRIORITY")
-        _wgrad_stream = _priority_stream(prio) if prio is not None else torch.cuda.Stream()
+        _wgrad_stream = torch.cuda.Stream()
     return _wgrad_stream
 
 
@@ -862,18 +838,13 @@ _join_queued = False
 # Operands of launches on the side stream must outlive them.  Tensor.record_stream() does that through the caching allocator (an
 # event per block, polled on later allocations: ~3 us of host time per tensor, ~200 tensors per step); holding a reference until the
 # compute stream has joined the side stream does the same for the price of a list append - and of memory: the gradients of a backward
-# pass then stay allocated until its end (cfg2: +2.8 GB).  XV2_SIDE_KEEP=0: record_stream.
-SIDE_KEEP = os.environ.get("XV2_SIDE_KEEP", "1") != "0"
+# pass then stay allocated until its end (cfg2: +2.8 GB).
 _side_keep = []
 
 
-def _keep_for_side(tensors, side):
-    if SIDE_KEEP and _join_queued:          # (a join is scheduled for the end of this backward pass: the references die there)
-        _side_keep.append(tensors)
-        return
-    for t in tensors:
-        if t is not None:
-            t.record_stream(side)
+def _keep_for_side(tensors):
+    # (only called with a join scheduled for the end of this backward pass - _conv_backward_weight: the references die there)
+    _side_keep.append(tensors)
 
 
 def begin_step():
@@ -898,8 +869,7 @@ def _conv_backward_weight(x0, x1, dy, weight, g, wparam=None, amax=None):
     # Asynchronous only for the first gradient a parameter receives in a step AND when it goes straight into the
     # flat buffer: autograd then merely adopts the tensor.  Any other case (plain autograd accumulation, shared
     # weights' second contribution) involves an accumulation kernel on the compute stream and stays in order.
-    side_ok = ASYNC_WGRAD and (WGRAD_SIDE == "all" or (WGRAD_SIDE == "3x3") == (g.kh * g.kw > 1))
-    out = grad_slot(weight if wparam is None else wparam) if side_ok else None
+    out = grad_slot(weight if wparam is None else wparam) if ASYNC_WGRAD else None
     if out is None:
         # Second (third ...) gradient of a SHARED weight in this step (SiameseUNet, ParallelUNet): the first one may
         # still be in flight on the side stream, and autograd's accumulation / the reducer's copy of the slot run on
@@ -945,7 +915,7 @@ def _conv_backward_weight(x0, x1, dy, weight, g, wparam=None, amax=None):
         side.wait_stream(torch.cuda.current_stream())          # dy (and x) are ready on the compute stream
         with torch.cuda.stream(side):
             dw = _conv_backward_weight_impl(x0, x1, dy, weight, g, wparam, out, amax)
-    _keep_for_side((x0, x1, dy), side)                     # keep the caching allocator from recycling them early
+    _keep_for_side((x0, x1, dy))                           # keep the caching allocator from recycling them early
     return dw
 
 
@@ -1063,12 +1033,11 @@ def _off(t, o):
     return None if t is None else Ptr(t, o)
 
 
-ZMASK = os.environ.get("XV2_ZMASK", "1") != "0"
 def _mask_ok(C, act, half=False):
     """layers whose activation follows a residual add can hand the backward pass a byte mask instead of z
     (W = channels per 16-byte lane of the BatchNorm kernels: 4 in fp32, 8 in bf16)"""
     W = 4          # channels per lane of the BatchNorm kernels (csrc/xv2_common.h Vec16: 4 for both storage types)
-    return (ZMASK and act in (ACT_RELU, ACT_LEAKY) and C % W == 0 and
+    return (act in (ACT_RELU, ACT_LEAKY) and C % W == 0 and
             (C % 256 == 0 or (C // W <= 256 and 256 % (C // W) == 0)))
 
 
@@ -1781,9 +1750,6 @@ class GateMulFn(torch.autograd.Function):
         return dskip, dgate
 
 
-SPLAT_TAIL = os.environ.get("XV2_SPLAT_TAIL", "1") != "0"      # the op-level tail behind one ABI call each way (xv2_splat_tail_*)
-
-
 class SplitAttentionFn(torch.autograd.Function):
     """ResNeSt radix-2 split attention on top of the (already BN+ReLU'd) grouped-conv output x
     [N,H,W,2C]: gap -> fc1 -> BN1 -> ReLU -> fc2 -> rSoftMax -> sum_r att_r * x_r.
@@ -1803,7 +1769,7 @@ class SplitAttentionFn(torch.autograd.Function):
         w1m, w2m = w1.reshape(inter, C).contiguous(), w2.reshape(C2, inter).contiguous()
         gap, att = _f32((N, C), x), _f32((N, C2), x)
         S = BN_SPLIT if (training and N % BN_SPLIT == 0) else 1
-        ctx.tail = (LAYER_CALLS and SPLAT_TAIL and BN_ROWS and N // S <= 64 and not (training and _sync_group(bn1)))
+        ctx.tail = (LAYER_CALLS and BN_ROWS and N // S <= 64 and not (training and _sync_group(bn1)))
         if ctx.tail:
             # the whole tail behind ONE ABI call (xv2_splat_tail_forward: the same six launches): the step of a deep ResNeSt
             # model is bound by the host's call rate; the small vectors live in one allocation
