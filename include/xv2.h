@@ -849,6 +849,46 @@ size_t xv2_building_table_workspace(int B, int H, int W);
 int xv2_building_table(const int32_t* labels, const uint8_t* dmg, const float* loc, int B, int H, int W, int max_rows,
                        void* workspace, int64_t* rows, int32_t* count, void* stream);
 
+/* ---- building outlines of a label map (polygons.hip, xview2_amd/utils/polygons.py) ------------------------------------
+ * Input and grid.  labels: int32 [B,H,W] as xv2_label_components writes them.  A pixel is foreground if it is inside the
+ * tile and its label is not 0.  Pixel (y,x) covers the square [x,x+1] x [y,y+1]; corners are the lattice points (x,y) with
+ * 0 <= x <= W and 0 <= y <= H.
+ * Boundary edges.  Side s of a foreground pixel p is a boundary edge if p's neighbour across that side is not foreground.
+ * Sides: 0 top, 1 right, 2 bottom, 3 left.  An edge is directed so that p is on its right: 0 heads east, 1 south, 2 west,
+ * 3 north (on screen, y down).  Its id is 4 (y W + x) + s.
+ * Successor.  With d the edge's direction, left(d) the direction a quarter turn to its left (left(E) = N), a = p + d and
+ * l = p + d + left(d): if a is not foreground the successor is side (s+1)%4 of p (a right turn); otherwise, if l is not
+ * foreground, side s of a (straight); otherwise side (s+3)%4 of l (a left turn).  Right-turn-first is 4-connectivity: two
+ * buildings touching at a corner stay two rings, two hole pixels touching at a corner form one ring that passes that
+ * corner twice.  The successor map is a permutation of the boundary edges; its cycles are the rings; all pixels on a
+ * ring's right belong to one component.
+ * Rings.  A ring's leader is its smallest edge id.  Its vertices are the end corners of those edges whose successor has a
+ * different side (collinear points are dropped, nothing else is simplified), in ring order starting at the leader edge.
+ * 2A = sum of x_i y_{i+1} - x_{i+1} y_i is positive for exterior rings and negative for holes.  A component's exterior
+ * ring is the one whose leader is 4 root + 0; the 2A of all rings of a component sum to twice its pixel area.
+ * Outputs.  xv2_polygon_count: counts int64 [B][2] = the numbers of boundary edges and of vertices per tile (both local
+ * properties: one launch and a scan); the host reads them once and sizes everything after them exactly.
+ * xv2_polygon_trace, with total_edges / total_vertices the sums of counts over the tiles:
+ *   verts       int32 [total_vertices][2] as (x,y): tiles in order, rings within a tile in ring-table order, each ring's
+ *               vertices contiguous
+ *   rings       int64 [total_vertices / 4][8]; rows ordered by tile, then ascending leader:
+ *               0 root (label - 1), 1 leader edge id, 2 number of vertices, 3 offset of the first vertex in verts,
+ *               4 2A (signed), 5 number of edges (the perimeter in pixels), 6 tile index, 7 0
+ *   ring_count  int32 [B]: the rings of every tile (every ring has at least 4 vertices, so the rows always suffice)
+ *   status      device int32, accumulated, never cleared: bit 0 is raised when the totals disagree with what the kernels
+ *               find; then ring_count is zeroed and nothing else is written
+ * Nothing beyond the counted rows and vertices is written; nothing is read back between the launches; every value is an
+ * integer and the same bits come out of every run.  Size limits as xv2_postprocess (H * W < 2^30, B <= 65535), and
+ * total_edges < 2^31; the workspace queries are 0 outside them.  Neither workspace needs clearing.  After a trace the first
+ * 32 bytes of its workspace hold, for diagnosis: int64 edges and vertices found, int32 ok, int32 pointer-doubling rounds
+ * that did work in the leader pass and in the ranking pass (each at most ceil(log2(total_edges))). */
+#define XV2_POLYGON_RING_COLS 8
+size_t xv2_polygon_count_workspace(int B, int H, int W);
+size_t xv2_polygon_trace_workspace(int B, int H, int W, int64_t total_edges);
+int xv2_polygon_count(const int32_t* labels, int B, int H, int W, void* workspace, int64_t* counts, void* stream);
+int xv2_polygon_trace(const int32_t* labels, int B, int H, int W, int64_t total_edges, int64_t total_vertices,
+                      void* workspace, int64_t* rings, int32_t* verts, int32_t* ring_count, int32_t* status, void* stream);
+
 /* ---- scene inference: windows of a scene of any size, blended on the device (xview2_amd/scene.py, scene.hip) ---------
  * A scene is H x W pixels, H * W < 2^30.  Windows are h x w (multiples of 32, 32..2048) with their origins (y0, x0) in a
  * device table; the table's order is the summation order.  tri(i, L) is reflection without repeating the edge, iterated:

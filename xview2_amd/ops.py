@@ -2390,3 +2390,50 @@ def building_table(labels, dmg, loc=None, max_rows=None):
     count = torch.empty((B,), dtype=torch.int32, device=labels.device)
     call("xv2_building_table", labels, dmg, loc, B, H, W, max_rows, ws, rows, count)
     return rows, count
+
+
+# ---- building outlines of a label map (csrc/polygons.hip) ----------------------------------------------------------------
+POLYGON_RING_COLS = 8
+
+
+def _polygon_labels(what, labels):
+    _need_cuda(labels)
+    if labels.dim() != 3 or labels.dtype != torch.int32:
+        raise ValueError("%s: labels must be int32 [B,H,W], got %s %s" % (what, labels.dtype, tuple(labels.shape)))
+    B, H, W = (int(v) for v in labels.shape)
+    if int(query("xv2_polygon_count_workspace", B, H, W)) == 0:
+        raise ValueError("%s: B=%d H=%d W=%d outside the supported sizes (H*W < 2^30, B <= 65535)" % (what, B, H, W))
+    return labels.contiguous(), B, H, W
+
+
+def polygon_count(labels):
+    """The numbers of boundary edges and of outline vertices per tile (include/xv2.h xv2_polygon_count).  labels: int32
+    [B,H,W] as label_components writes them.  Returns int64 [B, 2] on the device; its sums over the tiles are the totals
+    polygon_trace takes."""
+    labels, B, H, W = _polygon_labels("polygon_count", labels)
+    ws = _ws(int(query("xv2_polygon_count_workspace", B, H, W)), labels)
+    counts = torch.empty((B, 2), dtype=torch.int64, device=labels.device)
+    call("xv2_polygon_count", labels, B, H, W, ws, counts)
+    return counts
+
+
+def polygon_trace(labels, total_edges, total_vertices):
+    """The rings of a label map and their vertices (include/xv2.h xv2_polygon_trace).  total_edges, total_vertices: the
+    sums of polygon_count(labels) over the tiles.  Returns (rings int64 [total_vertices // 4, 8], verts int32
+    [total_vertices, 2], ring_count int32 [B]) on the device; rows ring_count.sum() and up of rings are not written.
+    Totals that are not the label map's raise RuntimeError."""
+    labels, B, H, W = _polygon_labels("polygon_trace", labels)
+    E, V = int(total_edges), int(total_vertices)
+    if not 0 <= V <= E < 2 ** 31:
+        raise ValueError("polygon_trace: totals must satisfy 0 <= total_vertices <= total_edges < 2^31, got %d edges and %d "
+                         "vertices" % (E, V))
+    ws = _ws(int(query("xv2_polygon_trace_workspace", B, H, W, E)), labels)
+    rings = torch.empty((V // 4, POLYGON_RING_COLS), dtype=torch.int64, device=labels.device)
+    verts = torch.empty((V, 2), dtype=torch.int32, device=labels.device)
+    ring_count = torch.empty((B,), dtype=torch.int32, device=labels.device)
+    status = torch.zeros((1,), dtype=torch.int32, device=labels.device)
+    call("xv2_polygon_trace", labels, B, H, W, E, V, ws, rings if V else None, verts if V else None, ring_count, status)
+    if int(status.item()):
+        raise RuntimeError("polygon_trace: the label map has other totals than %d edges and %d vertices; pass the sums of "
+                           "polygon_count of the same labels" % (E, V))
+    return rings, verts, ring_count

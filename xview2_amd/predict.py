@@ -7,7 +7,9 @@ pair is predicted window by window on the GPU (xview2_amd.scene) and written as 
 <stem>_damage_prediction.png, <stem> being the pre image's; --save_probs adds the blended maps as .npy.  With only one
 checkpoint only its map is written: the localization map is then the 0.3 threshold of post-processing, the damage map the
 decoded class of every pixel.  --buildings adds <stem>_buildings.csv (one row per predicted building: box, area, centroid,
-damage class, pixel counts, confidence) and <stem>_buildings.json (totals), computed on the GPU (xview2_amd.utils.buildings)."""
+damage class, pixel counts, confidence) and <stem>_buildings.json (totals), computed on the GPU (xview2_amd.utils.buildings).
+--polygons adds <stem>_buildings.geojson: the outline of every building with its holes, traced on the GPU from the same label
+map (xview2_amd.utils.polygons), with the table's row as properties; it implies --buildings."""
 import os
 from argparse import ArgumentDefaultsHelpFormatter, ArgumentParser
 
@@ -35,6 +37,8 @@ def get_parser():
     arg("--dilation_rate", type=int, default=3, help="dilation rate (odd)")
     arg("--save_probs", action="store_true", help="also write the blended probability maps as .npy")
     arg("--buildings", action="store_true", help="also write <stem>_buildings.csv / .json: one row per predicted building")
+    arg("--polygons", action="store_true", help="also write <stem>_buildings.geojson: one outline per predicted building "
+        "(implies --buildings)")
     return parser
 
 
@@ -122,13 +126,17 @@ def main(argv=None):
             Image.fromarray(pre_png.cpu().numpy()).save(stem + "_localization_prediction.png")
         if dmg is not None:
             Image.fromarray(post_png.cpu().numpy()).save(stem + "_damage_prediction.png")
-        if args.buildings:
+        if args.buildings or args.polygons:
             # from the maps the PNGs show (after --components and --dilate); confidence only with a localization model
             from .utils import buildings
-            rows = buildings.building_table(pre_png, post_png, loc_map if loc is not None else None)
+            rows, labels = buildings.building_table(pre_png, post_png, loc_map if loc is not None else None,
+                                                    return_labels=True)
             records = buildings.to_records(rows, H, W, confidence=loc is not None)
             buildings.write_csv(stem + "_buildings.csv", records)
             buildings.write_summary(stem + "_buildings.json", records)
+            if args.polygons:
+                from .utils import polygons
+                polygons.write_geojson(stem + "_buildings.geojson", polygons.building_polygons(pre_png, labels), records)
         if args.save_probs:
             if loc is not None:
                 np.save(stem + "_localization_probs.npy", loc_maps.cpu().numpy())

@@ -21,11 +21,12 @@ def first_capacity(H, W):
     return max(MIN_ROWS, H * W // PIXELS_PER_ROW)
 
 
-def building_table(pre, post, loc=None, capacity=None):
+def building_table(pre, post, loc=None, capacity=None, return_labels=False):
     """pre, post: uint8 [H,W] or [B,H,W] device maps (the label maps of the two PNGs); loc: fp32 probabilities of the same
     shape or None.  Returns numpy int64 [n_b, 16] per tile (a list; one array for unbatched input), rows in
     scipy.ndimage.label's order.  capacity: first row capacity per tile (default first_capacity(H, W)); a tile with more
-    buildings makes the kernels run once more with the capacity its count asks for."""
+    buildings makes the kernels run once more with the capacity its count asks for.  return_labels: also return the int32
+    device labels of pre != 0 the table was built from (utils.polygons traces the outlines from them)."""
     import torch
     from .. import ops
     single = pre.dim() == 2
@@ -47,6 +48,8 @@ def building_table(pre, post, loc=None, capacity=None):
         n = count.cpu().numpy()
     host = rows[:, :int(n.max())].cpu().numpy()
     out = [np.ascontiguousarray(host[b, :int(n[b])]) for b in range(B)]
+    if return_labels:
+        return (out[0], labels[0]) if single else (out, labels)
     return out[0] if single else out
 
 

@@ -18,10 +18,12 @@ Semantics are the reference's (post_process.py:27-47), bit for bit, with these d
      output: 0..255 without --components, 1..4 with it (the vote keeps four classes per building); otherwise
      ValueError, where the reference would vote over it and write a PNG its scorer rejects.
 
-    python -m xview2_amd.utils.post_process --results R [--components] [--dilate [--dilation_rate 3]] [--buildings]
+    python -m xview2_amd.utils.post_process --results R [--components] [--dilate [--dilation_rate 3]] [--buildings] [--polygons]
 
 --buildings also writes buildings/test_buildings_NNNNN.csv per pair: one row per predicted building of the two PNGs
-(xview2_amd.utils.buildings), its confidence from the localization probabilities.
+(xview2_amd.utils.buildings), its confidence from the localization probabilities.  --polygons (which implies --buildings)
+adds buildings/test_buildings_NNNNN.geojson: the outline of every building, traced from the same label map
+(xview2_amd.utils.polygons).
 """
 import os
 from argparse import ArgumentDefaultsHelpFormatter, ArgumentParser, ArgumentTypeError
@@ -128,13 +130,20 @@ def run(args):
                     workspace[key] = ops.postprocess_workspace(len(ks), lshape[0], lshape[1], args.components, dev)
                 pre, post = ops.postprocess(loc, dmg, components=args.components, rate=rate,
                                             workspace=workspace.get(key))
-                if getattr(args, "buildings", False):
+                want_polygons = getattr(args, "polygons", False)
+                if getattr(args, "buildings", False) or want_polygons:
                     from . import buildings
                     os.makedirs(os.path.join(args.results, "buildings"), exist_ok=True)
-                    for j, rows in enumerate(buildings.building_table(pre, post, loc)):
+                    tables, labels = buildings.building_table(pre, post, loc, return_labels=True)
+                    if want_polygons:
+                        from . import polygons
+                        outlines = polygons.building_polygons(pre, labels)
+                    for j, rows in enumerate(tables):
                         recs = buildings.to_records(rows, lshape[0], lshape[1])
-                        pending.append(pool.submit(buildings.write_csv, os.path.join(
-                            args.results, "buildings", _buildings_name(pairs[ks[j]][0])), recs))
+                        name = os.path.join(args.results, "buildings", _buildings_name(pairs[ks[j]][0]))
+                        pending.append(pool.submit(buildings.write_csv, name, recs))
+                        if want_polygons:
+                            pending.append(pool.submit(polygons.write_geojson, name[:-4] + ".geojson", outlines[j], recs))
                 pre, post = pre.cpu().numpy(), post.cpu().numpy()
                 for j, k in enumerate(ks):
                     a, b = pairs[k]
@@ -161,6 +170,8 @@ def get_parser():
     arg("--results", type=str, default="/results", help="Directory holding probs/; predictions/ is written there")
     arg("--batch", type=_positive_int, default=8, help="Tiles per GPU call")
     arg("--buildings", action="store_true", help="Also write buildings/<name>.csv per pair: one row per predicted building")
+    arg("--polygons", action="store_true", help="Also write buildings/<name>.geojson per pair: one outline per predicted "
+        "building (implies --buildings)")
     return parser
 
 
