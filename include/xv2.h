@@ -394,6 +394,37 @@ int xv2_bn_act_backward(const void* dz, int lddz, const void* z, int ldz, const 
                         const float* scale, const float* shift, int act, double count, void* dy, int lddy,
                         void* dres, int lddres, int64_t npix, int C, double* sums2, float* dgamma,
                         float* dbeta, float* workspace, int dtype, void* stream);
+/* ---- shortcut fusion: the projection shortcut's BatchNorm inside the bottleneck block's last BatchNorm passes ----
+ * A bottleneck block with a projection shortcut (torchvision Bottleneck / ResNeSt Bottleneck with `downsample`: layer1.0 ..
+ * layer4.0) ends in z = act(BN3(conv3(a)) + BN_ds(conv_ds(x))).  The shortcut's normalised output idt = BN_ds(y_ds) has one
+ * consumer, BN3's apply pass, and the residual gradient dres that pass sends back has one consumer, BN_ds's backward - both are
+ * elementwise functions of what the neighbouring pass holds in registers, so neither tensor is stored (five tensor passes and four
+ * launches less per block and step):
+ *   xv2_bn_act_shortcut_forward  (replaces xv2_bn_act_forward of the shortcut + xv2_bn_act_forward_mask of conv3's layer): one
+ *     pass over y3 and y_ds writes z, the byte mask of z and records max |z| (xv2_amax_ctx `out`); idt is rounded to the storage
+ *     type the way the unfused pass stores it.
+ *   xv2_bn_act_shortcut_backward (replaces xv2_bn_act_backward of both layers): one column pass takes both layers' (sum g,
+ *     sum g * xhat) - g = dz * act'(mask) for BN3, g rounded to the storage type (the stored dres) for the shortcut - in the row
+ *     chunks of the unfused passes; ONE statistics fold over 2C channels (sums2: [2C][2] doubles, BN3's channels first); one apply
+ *     pass writes dy3 and dy_ds, the four parameter-gradient vectors (the fp64 sums rounded to fp32) and records max |dy3|
+ *     (xv2_amax_ctx `out`) and max |dy_ds| (amax_dy_ds: 64 slots like `out`, zero beforehand, or NULL).
+ *     workspace: xv2_bn_act_shortcut_backward_workspace(npix, C) bytes.
+ *   z, the mask, dy3, dy_ds, both layers' sums, dgamma, dbeta and the recorded maxima are bit-identical to the unfused calls.
+ * Shapes: xv2_bn_act_shortcut_supported(npix, C, dtype) - the vector path of the column sums (C % 4 == 0 and C / 4 divides 256, or
+ * C a multiple of 256); both tensors dense [npix][C] in the same storage type, 16-byte aligned; ReLU / LeakyReLU; single-process
+ * training-mode BatchNorm of one batch.  The Python layer takes this path for the tail of Bottleneck / StBottleneck
+ * (nn.bottleneck_tail); XV2_SHORTCUT_FUSE=0 in the environment restores the unfused calls (A/B runs). */
+int xv2_bn_act_shortcut_supported(int64_t npix, int C, int dtype);
+int xv2_bn_act_shortcut_forward(const void* y3, const void* y_ds, const float* scale3, const float* shift3,
+                                const float* scale_ds, const float* shift_ds, int act, void* z, uint8_t* zmask,
+                                int64_t npix, int C, int dtype, void* stream);
+size_t xv2_bn_act_shortcut_backward_workspace(int64_t npix, int C);
+int xv2_bn_act_shortcut_backward(const void* dz, const uint8_t* zmask, const void* y3, const void* y_ds,
+                                 const float* mean3, const float* invstd3, const float* gamma3, const float* mean_ds,
+                                 const float* invstd_ds, const float* gamma_ds, int act, double count, void* dy3,
+                                 void* dy_ds, int64_t npix, int C, double* sums2, float* dgamma3, float* dbeta3,
+                                 float* dgamma_ds, float* dbeta_ds, void* amax_dy_ds, float* workspace, int dtype,
+                                 void* stream);
 
 /* ---- pooling / resampling ----------------------------------------------------------------- */
 /* nn.MaxPool2d(3,2,1) (model/unet.py:81); idx = argmax tap (first maximum in scan order).  Backward passes of the pooling

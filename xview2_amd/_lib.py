@@ -75,7 +75,7 @@ def lib():
         _lib.xv2_last_error.restype = ctypes.c_char_p
         for name in ("xv2_conv2d_backward_weight_workspace", "xv2_conv2d_forward_workspace",
                      "xv2_conv2d_backward_data_workspace", "xv2_head_conv_backward_workspace",
-                     "xv2_bn_tensor_stats_workspace", "xv2_bn_backward_workspace", "xv2_bn_act_head_backward_workspace", "xv2_splat_gap_workspace",
+                     "xv2_bn_tensor_stats_workspace", "xv2_bn_backward_workspace", "xv2_bn_act_head_backward_workspace", "xv2_bn_act_shortcut_backward_workspace", "xv2_splat_gap_workspace",
                      "xv2_loss_workspace", "xv2_ohem_workspace", "xv2_sort_workspace", "xv2_lovasz_workspace", "xv2_xchg_bytes", "xv2_presplit_f16_bytes", "xv2_postprocess_workspace",
                      "xv2_autoaugment_workspace", "xv2_building_table_workspace", "xv2_polygon_count_workspace",
                      "xv2_polygon_trace_workspace"):

@@ -857,6 +857,211 @@ __global__ void __launch_bounds__(256) bn_act_bwd_rows_head_kernel(const HeadGra
     if (amax) amax_record(amax, dmax, amax_red);
 }
 
+// ---- the projection shortcut of a bottleneck block inside the block's last BatchNorm passes (include/xv2.h "shortcut fusion") ----
+// z = act(BN3(y3) + BN_ds(y_ds)): the shortcut's normalised output r (forward) and the residual gradient (backward) are pure
+// functions of what the neighbouring pass of BN3 already holds in registers, so neither tensor is stored.  Every value the unfused
+// launches store and read back (r, the residual gradient) passes through stored4<T> + as_loaded here; the sums and dy are spelled
+// with explicit fmas the way the unfused kernels contract them: all results are bit-identical to the launches replaced.
+// Dense tensors, the vector path of chunk_geom, 4 channels per lane.
+
+// forward apply of both BatchNorms: bn_act_fwd_kernel<true>'s walk (rev), mask byte and maximum record
+template <typename T>
+__global__ void __launch_bounds__(256) bn_act_shortcut_fwd_kernel(const T* __restrict__ y3, const T* __restrict__ yd,
+                                                                   const float* __restrict__ scale3, const float* __restrict__ shift3,
+                                                                   const float* __restrict__ scaled, const float* __restrict__ shiftd,
+                                                                   int act, T* __restrict__ z, int64_t npix, int C,
+                                                                   uint8_t* __restrict__ zmask, int rev, unsigned* __restrict__ amax) {
+    __shared__ float amax_red[4];
+    float zmax = 0.f;
+    const int CW = C / 4;
+    const int64_t total = npix * CW;
+    for (int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; j < total; j += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t i = rev ? total - 1 - j : j;
+        const int64_t row = i / CW;
+        const int c = (int)(i - row * CW) * 4;
+        const float4 v3 = ld4(y3 + row * C + c), vd = ld4(yd + row * C + c);
+        const float4 sc3 = *reinterpret_cast<const float4*>(scale3 + c), sh3 = *reinterpret_cast<const float4*>(shift3 + c);
+        const float4 scd = *reinterpret_cast<const float4*>(scaled + c), shd = *reinterpret_cast<const float4*>(shiftd + c);
+        // the shortcut's output as its own apply pass stores it (no residual, no activation) and BN3's apply pass loads it
+        const float4 r = as_loaded(stored4<T>(bn_act_apply4(vd, scd, shd, nullptr, XV2_ACT_NONE)));
+        const float4 o = bn_act_apply4(v3, sc3, sh3, &r, act);
+        zmax = amax_acc(zmax, o);
+        st4(z + row * C + c, o);
+        zmask[i] = (uint8_t)((o.x > 0.f) | ((o.y > 0.f) << 1) | ((o.z > 0.f) << 2) | ((o.w > 0.f) << 3));
+    }
+    if (amax) amax_record(amax, zmax, amax_red);
+}
+
+struct ShortcutBn {      // one BatchNorm of the pair, as the backward passes see it
+    const float* mean;
+    const float* invstd;
+    const float* gamma;
+};
+
+// Column pass with two sum pairs: column_partials_kernel<1>'s chunk -> rows -> partial-row mapping, its two rows in flight and
+// its in-block fold, once for BN3 (sum g, sum g * xhat3: mode 1 with the byte mask) and once for the shortcut (sum gs, sum gs *
+// xhat_ds: mode 1 with act = NONE and z == nullptr, reading the stored residual gradient gs).  part: [chunk][2C][2], BN3's channels
+// first - reduce_stats<double> then folds both layers in one launch over 2C channels.
+template <typename T>
+__global__ void __launch_bounds__(256) column_partials_shortcut_kernel(const T* __restrict__ dz, const uint8_t* __restrict__ zmask,
+                                                                        const T* __restrict__ y3, const T* __restrict__ yd,
+                                                                        const ShortcutBn b3, const ShortcutBn bd, int act,
+                                                                        int64_t npix, int C, int rpb, int cgw,
+                                                                        double* __restrict__ part, int rev) {
+    __shared__ float sh3[256 * 8];
+    __shared__ float shd[256 * 8];
+    const int tid = threadIdx.x;
+    const int chunk = rev ? gridDim.x - 1 - blockIdx.x : blockIdx.x;
+    const int64_t r0 = (int64_t)chunk * rpb;
+    const int64_t r1 = min(r0 + (int64_t)rpb, npix);
+    double* out = part + (size_t)chunk * C * 4;
+    const int CW = cgw / 4, c4tot = C / 4;
+    const int rpp = 256 / CW;
+    const int tx = tid % CW, ty = tid / CW;
+    const int cb = blockIdx.y * cgw + tx * 4;
+    const float4 mu3 = *reinterpret_cast<const float4*>(b3.mean + cb), is3 = *reinterpret_cast<const float4*>(b3.invstd + cb);
+    const float4 mud = *reinterpret_cast<const float4*>(bd.mean + cb), isd = *reinterpret_cast<const float4*>(bd.invstd + cb);
+    const float4 zero = make_float4(0, 0, 0, 0);
+    float4 f0 = zero, f1 = zero, g0 = zero, g1 = zero;      // BN3: two rows in flight
+    float4 h0 = zero, h1 = zero, k0 = zero, k1 = zero;      // shortcut
+    auto rowsum = [&](int64_t r, float4& a0, float4& a1, float4& s0, float4& s1) {
+        const float4 d = ld4(dz + r * C + cb), v3 = ld4(y3 + r * C + cb), vd = ld4(yd + r * C + cb);
+        const unsigned m = zmask[r * c4tot + (cb >> 2)];
+        const float ax = act_grad_from_output((m & 1u) ? 1.f : -1.f, act), ay = act_grad_from_output((m & 2u) ? 1.f : -1.f, act);
+        const float az = act_grad_from_output((m & 4u) ? 1.f : -1.f, act), aw = act_grad_from_output((m & 8u) ? 1.f : -1.f, act);
+        // BN3's sums as mode 1 contracts them: the product of a0's term unrounded inside an fma, a1's g rounded first
+        const float4 g = as_loaded(make_float4(d.x * ax, d.y * ay, d.z * az, d.w * aw));
+        a0.x = __fmaf_rn(d.x, ax, a0.x); a0.y = __fmaf_rn(d.y, ay, a0.y); a0.z = __fmaf_rn(d.z, az, a0.z); a0.w = __fmaf_rn(d.w, aw, a0.w);
+        const float4 x3 = as_loaded(make_float4((v3.x - mu3.x) * is3.x, (v3.y - mu3.y) * is3.y, (v3.z - mu3.z) * is3.z, (v3.w - mu3.w) * is3.w));
+        a1.x = __fmaf_rn(g.x, x3.x, a1.x); a1.y = __fmaf_rn(g.y, x3.y, a1.y); a1.z = __fmaf_rn(g.z, x3.z, a1.z); a1.w = __fmaf_rn(g.w, x3.w, a1.w);
+        // the shortcut's: gs = the residual gradient as stored and read back; its activation gradient is 1 (gs * 1 is exact)
+        const float4 gs = as_loaded(stored4<T>(g));
+        s0.x = __fmaf_rn(gs.x, 1.f, s0.x); s0.y = __fmaf_rn(gs.y, 1.f, s0.y); s0.z = __fmaf_rn(gs.z, 1.f, s0.z); s0.w = __fmaf_rn(gs.w, 1.f, s0.w);
+        const float4 xd = as_loaded(make_float4((vd.x - mud.x) * isd.x, (vd.y - mud.y) * isd.y, (vd.z - mud.z) * isd.z, (vd.w - mud.w) * isd.w));
+        s1.x = __fmaf_rn(gs.x, xd.x, s1.x); s1.y = __fmaf_rn(gs.y, xd.y, s1.y); s1.z = __fmaf_rn(gs.z, xd.z, s1.z); s1.w = __fmaf_rn(gs.w, xd.w, s1.w);
+    };
+    int64_t r = r0 + ty;
+    for (; r + rpp < r1; r += 2 * rpp) {
+        rowsum(r, f0, f1, h0, h1);
+        rowsum(r + rpp, g0, g1, k0, k1);
+    }
+    if (r < r1) rowsum(r, f0, f1, h0, h1);
+    f0.x += g0.x; f0.y += g0.y; f0.z += g0.z; f0.w += g0.w;
+    f1.x += g1.x; f1.y += g1.y; f1.z += g1.z; f1.w += g1.w;
+    h0.x += k0.x; h0.y += k0.y; h0.z += k0.z; h0.w += k0.w;
+    h1.x += k1.x; h1.y += k1.y; h1.z += k1.z; h1.w += k1.w;
+    *reinterpret_cast<float4*>(sh3 + tid * 8) = f0;
+    *reinterpret_cast<float4*>(sh3 + tid * 8 + 4) = f1;
+    *reinterpret_cast<float4*>(shd + tid * 8) = h0;
+    *reinterpret_cast<float4*>(shd + tid * 8 + 4) = h1;
+    __syncthreads();
+    if (tid < 2 * CW) {          // one thread per 4-channel group and BatchNorm
+        const int lane = tid % CW;
+        const float* s = tid < CW ? sh3 : shd;
+        double a0[4] = {0, 0, 0, 0}, a1[4] = {0, 0, 0, 0};
+        for (int rr = 0; rr < rpp; ++rr) {
+            const float* t = s + (rr * CW + lane) * 8;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                a0[k] += t[k];
+                a1[k] += t[4 + k];
+            }
+        }
+        double* o = out + ((tid < CW ? 0 : C) + blockIdx.y * cgw + lane * 4) * 2;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            o[2 * k] = a0[k];
+            o[2 * k + 1] = a1[k];
+        }
+    }
+}
+
+// Backward apply with two outputs: bn_act_bwd_rows_kernel's geometry, walk (rev) and expressions (g and xhat rounded, then one
+// fma), dy3 from g and dy_ds from the stored form gs of the same g; the residual gradient itself is not written.  sums2: [2C][2],
+// BN3's channels first.  The two maxima go to two slot sets; dgamma / dbeta of each layer go to that layer's own vector.
+template <typename T>
+__global__ void __launch_bounds__(256) bn_act_shortcut_bwd_rows_kernel(const T* __restrict__ dz, const uint8_t* __restrict__ zmask,
+                                                                        const T* __restrict__ y3, const T* __restrict__ yd,
+                                                                        const ShortcutBn b3, const ShortcutBn bd,
+                                                                        const double* __restrict__ sums2, double count, int act,
+                                                                        T* __restrict__ dy3, T* __restrict__ dyd, int64_t npix, int C,
+                                                                        int cgw, int rows_per_block, int rev,
+                                                                        float* __restrict__ dgamma3, float* __restrict__ dbeta3,
+                                                                        float* __restrict__ dgammad, float* __restrict__ dbetad,
+                                                                        unsigned* __restrict__ amax3, unsigned* __restrict__ amaxd) {
+    __shared__ float amax_red[4];
+    float max3 = 0.f, maxd = 0.f;
+    const int CW = cgw / 4, rpp = 256 / CW, c4tot = C / 4;
+    const int tx = threadIdx.x % CW, ty = threadIdx.x / CW;
+    const int c = blockIdx.y * cgw + tx * 4;
+    const float inv_count = (float)(1.0 / count);
+    float gi3[4], mu3[4], is3[4], sg3[4], sgx3[4], gid[4], mud[4], isd[4], sgd[4], sgxd[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        is3[k] = b3.invstd[c + k];
+        mu3[k] = b3.mean[c + k];
+        gi3[k] = (b3.gamma ? b3.gamma[c + k] : 1.f) * is3[k];
+        sg3[k] = (float)sums2[(c + k) * 2] * inv_count;
+        sgx3[k] = (float)sums2[(c + k) * 2 + 1] * inv_count;
+        isd[k] = bd.invstd[c + k];
+        mud[k] = bd.mean[c + k];
+        gid[k] = (bd.gamma ? bd.gamma[c + k] : 1.f) * isd[k];
+        sgd[k] = (float)sums2[(C + c + k) * 2] * inv_count;
+        sgxd[k] = (float)sums2[(C + c + k) * 2 + 1] * inv_count;
+        // the parameter gradients are the fp64 sums rounded to fp32 (what reduce_stats writes next to them): the first row block
+        // delivers them to the two layers' own vectors
+        if (blockIdx.x == 0 && ty == 0) {
+            if (dbeta3) dbeta3[c + k] = (float)sums2[(c + k) * 2];
+            if (dgamma3) dgamma3[c + k] = (float)sums2[(c + k) * 2 + 1];
+            if (dbetad) dbetad[c + k] = (float)sums2[(C + c + k) * 2];
+            if (dgammad) dgammad[c + k] = (float)sums2[(C + c + k) * 2 + 1];
+        }
+    }
+    const int64_t r0 = (int64_t)(rev ? gridDim.x - 1 - blockIdx.x : blockIdx.x) * rows_per_block;
+    const int64_t r1 = min(r0 + (int64_t)rows_per_block, npix);
+    for (int64_t r = r0 + ty; r < r1; r += rpp) {
+        const float4 dv = ld4(dz + r * C + c), v3 = ld4(y3 + r * C + c), vd = ld4(yd + r * C + c);
+        const unsigned m = zmask[r * c4tot + (c >> 2)];
+        const float* d = reinterpret_cast<const float*>(&dv);
+        const float* yy3 = reinterpret_cast<const float*>(&v3);
+        const float* yyd = reinterpret_cast<const float*>(&vd);
+        float4 gv;
+        float* g = reinterpret_cast<float*>(&gv);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) g[k] = d[k] * act_grad_from_output(((m >> k) & 1u) ? 1.f : -1.f, act);
+        gv = as_loaded(gv);
+        const float4 gsv = as_loaded(stored4<T>(gv));      // the residual gradient as stored and read back
+        const float* gs = reinterpret_cast<const float*>(&gsv);
+        float4 x3v, xdv;
+        float* x3 = reinterpret_cast<float*>(&x3v);
+        float* xd = reinterpret_cast<float*>(&xdv);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            x3[k] = (yy3[k] - mu3[k]) * is3[k];
+            xd[k] = (yyd[k] - mud[k]) * isd[k];
+        }
+        x3v = as_loaded(x3v);
+        xdv = as_loaded(xdv);
+        float4 o3v, odv;
+        float* o3 = reinterpret_cast<float*>(&o3v);
+        float* od = reinterpret_cast<float*>(&odv);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            o3[k] = gi3[k] * __fmaf_rn(-x3[k], sgx3[k], g[k] - sg3[k]);
+            od[k] = gid[k] * __fmaf_rn(-xd[k], sgxd[k], gs[k] - sgd[k]);
+        }
+        max3 = amax_acc(max3, o3v);
+        maxd = amax_acc(maxd, odv);
+        st4(dy3 + r * C + c, o3v);
+        st4(dyd + r * C + c, odv);
+    }
+    if (amax3) amax_record(amax3, max3, amax_red);
+    if (amaxd) {
+        __syncthreads();      // amax_red is read by thread 0 of the first record
+        amax_record(amaxd, maxd, amax_red);
+    }
+}
+
 // BatchNorm over a HANDFUL of rows (split attention's bn1 on the [N, inter] vector of pooled features, N = the batch:
 // ResNeSt SplAtConv2d, model/unet.py:52): statistics, running-statistics update, coefficients, normalise + activation in
 // ONE launch, one thread per channel (two-pass fp64 statistics over its <= 64 rows).  Replaces the five launches of the
@@ -1405,4 +1610,111 @@ extern "C" int xv2_bn_rows_backward(const float* dz, const float* z, const float
                        invstd, gamma, rows, C, parts, act, train, dy, dgamma, dbeta);
     XV2_CHECK_LAUNCH();
     return XV2_OK;
+}
+
+// ---- the projection shortcut's BatchNorm inside the block's last BatchNorm passes (include/xv2.h "shortcut fusion") ----
+static int shortcut_prof_id(int which) {      // bench-time profiler names of the three fused kernels
+    static const int ids[3] = {prof_register("bn_act_shortcut_fwd_kernel"), prof_register("column_partials_shortcut_kernel"),
+                               prof_register("bn_act_shortcut_bwd_rows_kernel")};
+    return ids[which];
+}
+
+extern "C" int xv2_bn_act_shortcut_supported(int64_t npix, int C, int dtype) {
+    if (npix <= 0 || C <= 0 || (dtype != XV2_F32 && dtype != XV2_BF16)) return 0;
+    // the vector path of the column sums (4 channels per lane for both storage types: Vec16), which is also the shape rule of the
+    // byte mask and of the streaming apply pass
+    return chunk_geom(npix, C, 4).cgw ? 1 : 0;
+}
+
+template <typename T>
+static int bn_act_shortcut_forward_impl(const T* y3, const T* yd, const float* scale3, const float* shift3, const float* scaled,
+                                        const float* shiftd, int act, T* z, uint8_t* zmask, int64_t npix, int C, hipStream_t st) {
+    XV2_CHECK_ARG(vec_ok(C, sizeof(T), {}, {y3, yd, z}, 4) && vec_ok(C, 4, {}, {scale3, shift3, scaled, shiftd}),
+                  "bn_act_shortcut_forward: unaligned operand");
+    unsigned* amax = std::is_same<T, float>::value ? amax_ctx().out : nullptr;      // F16X2: record max |z| (fp32 tensors)
+    const int grid = ew_grid(npix * (C / 4));
+    prof_begin(shortcut_prof_id(0), 0.0, 0.0, st);
+    hipLaunchKernelGGL(bn_act_shortcut_fwd_kernel<T>, dim3(grid), dim3(256), 0, st, y3, yd, scale3, shift3, scaled, shiftd, act, z,
+                       npix, C, zmask, BN_REV_FWD_APPLY, amax);
+    prof_end(st);
+    XV2_CHECK_LAUNCH();
+    return XV2_OK;
+}
+
+extern "C" int xv2_bn_act_shortcut_forward(const void* y3, const void* y_ds, const float* scale3, const float* shift3,
+                                           const float* scale_ds, const float* shift_ds, int act, void* z, uint8_t* zmask,
+                                           int64_t npix, int C, int dtype, void* stream) {
+    XV2_CHECK_DTYPE(dtype);
+    AmaxGuard amax_guard;
+    XV2_CHECK_ARG(y3 && y_ds && scale3 && shift3 && scale_ds && shift_ds && z && zmask, "bn_act_shortcut_forward: null argument");
+    XV2_CHECK_ARG(act == XV2_ACT_RELU || act == XV2_ACT_LEAKY, "bn_act_shortcut_forward: ReLU-type activation only (got %d)", act);
+    XV2_CHECK_ARG(xv2_bn_act_shortcut_supported(npix, C, dtype), "bn_act_shortcut_forward: no fused form for C=%d", C);
+    XV2_DISPATCH_DTYPE(dtype, return bn_act_shortcut_forward_impl<T>((const T*)y3, (const T*)y_ds, scale3, shift3, scale_ds, shift_ds,
+                                                                    act, (T*)z, zmask, npix, C, (hipStream_t)stream));
+}
+
+// partials [chunks][2C][2] doubles, then reduce_stats' scratch rows for 2C channels
+static size_t bn_shortcut_part_bytes(int64_t npix, int C) {
+    const size_t part = (size_t)chunk_geom(npix, C, 4).chunks * C * 4 * sizeof(double);
+    return (part + 15) & ~(size_t)15;
+}
+extern "C" size_t xv2_bn_act_shortcut_backward_workspace(int64_t npix, int C) {
+    if (npix <= 0 || C <= 0) return 0;
+    return bn_shortcut_part_bytes(npix, C) + (size_t)XV2_BN_SCRATCH_ROWS * C * 4 * sizeof(double);
+}
+
+template <typename T>
+static int bn_act_shortcut_backward_impl(const T* dz, const uint8_t* zmask, const T* y3, const T* yd, const ShortcutBn& b3,
+                                         const ShortcutBn& bd, int act, double count, T* dy3, T* dyd, int64_t npix, int C,
+                                         double* sums2, float* dgamma3, float* dbeta3, float* dgammad, float* dbetad,
+                                         unsigned* amax_dyd, float* workspace, hipStream_t st) {
+    XV2_CHECK_ARG(vec_ok(C, sizeof(T), {}, {dz, y3, yd, dy3, dyd}, 4) &&
+                      vec_ok(C, 4, {}, {b3.mean, b3.invstd, b3.gamma, bd.mean, bd.invstd, bd.gamma}),
+                  "bn_act_shortcut_backward: unaligned operand");
+    const bool f32 = std::is_same<T, float>::value;      // F16X2: record max |dy3| / max |dy_ds| (fp32 tensors)
+    unsigned* amax3 = f32 ? amax_ctx().out : nullptr;
+    unsigned* amaxd = f32 ? amax_dyd : nullptr;
+    const ChunkGeom g = chunk_geom(npix, C, 4);
+    double* dpart = reinterpret_cast<double*>(workspace);
+    double* scratch = reinterpret_cast<double*>(reinterpret_cast<char*>(workspace) + bn_shortcut_part_bytes(npix, C));
+    // pass 1: both layers' (sum g, sum g * xhat) per channel in the unfused passes' row chunks; one fold over 2C channels
+    prof_begin(shortcut_prof_id(1), 0.0, 0.0, st);
+    hipLaunchKernelGGL(column_partials_shortcut_kernel<T>, dim3((unsigned)g.chunks, g.groups), dim3(256), 0, st, dz, zmask, y3, yd, b3,
+                       bd, act, npix, C, g.rpb, g.cgw, dpart, BN_REV_COLUMN_SUMS);
+    prof_end(st);
+    XV2_CHECK_LAUNCH();
+    int rc = reduce_stats<double>(dpart, g.chunks, 2 * C, sums2, scratch, st);
+    if (rc) return rc;
+    // pass 2: dy3 and dy_ds in the row blocks of bn_act_bwd_rows_kernel
+    const int rpp = 256 / (g.cgw / 4);
+    int64_t rpb = cdiv(npix * g.groups, sizeof(T) == 2 ? 2048 : 4096);
+    rpb = std::max<int64_t>(cdiv(rpb, rpp) * rpp, rpp * 4);
+    prof_begin(shortcut_prof_id(2), 0.0, 0.0, st);
+    hipLaunchKernelGGL(bn_act_shortcut_bwd_rows_kernel<T>, dim3((unsigned)cdiv(npix, rpb), g.groups), dim3(256), 0, st, dz, zmask, y3,
+                       yd, b3, bd, sums2, count, act, dy3, dyd, npix, C, g.cgw, (int)rpb, BN_REV_BWD_APPLY, dgamma3, dbeta3, dgammad,
+                       dbetad, amax3, amaxd);
+    prof_end(st);
+    XV2_CHECK_LAUNCH();
+    return XV2_OK;
+}
+
+extern "C" int xv2_bn_act_shortcut_backward(const void* dz, const uint8_t* zmask, const void* y3, const void* y_ds,
+                                            const float* mean3, const float* invstd3, const float* gamma3, const float* mean_ds,
+                                            const float* invstd_ds, const float* gamma_ds, int act, double count, void* dy3,
+                                            void* dy_ds, int64_t npix, int C, double* sums2, float* dgamma3, float* dbeta3,
+                                            float* dgamma_ds, float* dbeta_ds, void* amax_dy_ds, float* workspace, int dtype,
+                                            void* stream) {
+    XV2_CHECK_DTYPE(dtype);
+    AmaxGuard amax_guard;
+    XV2_CHECK_ARG(dz && zmask && y3 && y_ds && mean3 && invstd3 && mean_ds && invstd_ds && dy3 && dy_ds && sums2 && workspace,
+                  "bn_act_shortcut_backward: null argument");
+    XV2_CHECK_ARG(act == XV2_ACT_RELU || act == XV2_ACT_LEAKY, "bn_act_shortcut_backward: ReLU-type activation only (got %d)", act);
+    XV2_CHECK_ARG(xv2_bn_act_shortcut_supported(npix, C, dtype), "bn_act_shortcut_backward: no fused form for C=%d", C);
+    ShortcutBn b3, bd;
+    b3.mean = mean3; b3.invstd = invstd3; b3.gamma = gamma3;
+    bd.mean = mean_ds; bd.invstd = invstd_ds; bd.gamma = gamma_ds;
+    XV2_DISPATCH_DTYPE(dtype, return bn_act_shortcut_backward_impl<T>((const T*)dz, zmask, (const T*)y3, (const T*)y_ds, b3, bd, act,
+                                                                     count, (T*)dy3, (T*)dy_ds, npix, C, sums2, dgamma3, dbeta3,
+                                                                     dgamma_ds, dbeta_ds, (unsigned*)amax_dy_ds, workspace,
+                                                                     (hipStream_t)stream));
 }

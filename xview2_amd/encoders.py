@@ -42,15 +42,16 @@ class Bottleneck(nn.Module):
             out = xnn.conv_bn_act(self.conv1, self.bn1, x, act=ops.ACT_RELU)
         out = xnn.conv_bn_act(self.conv2, self.bn2, out, act=ops.ACT_RELU)
         if self.downsample is None:
-            idt = x
-        elif fuse and self.alias_request:
+            return xnn.conv_bn_act(self.conv3, self.bn3, out, act=ops.ACT_RELU, residual=x)
+        # projection shortcut: its BatchNorm runs inside conv3's BatchNorm passes (xnn.bottleneck_tail)
+        if fuse and self.alias_request:
             # a THIRD consumer of the block input (the decoder's skip connection) reads the shortcut convolution's alias: its
             # gradient is summed in that convolution's backward-data epilogue (for the stride-2 shortcut also instead of the
             # memset of the pixels no tap reaches)
-            idt, self.alias_out = xnn.conv_bn_act(self.downsample[0], self.downsample[1], x, passthrough=True)
-        else:
-            idt = xnn.conv_bn_act(self.downsample[0], self.downsample[1], x)
-        return xnn.conv_bn_act(self.conv3, self.bn3, out, act=ops.ACT_RELU, residual=idt)
+            z, self.alias_out = xnn.bottleneck_tail(self.conv3, self.bn3, out, self.downsample[0], self.downsample[1], x,
+                                                    passthrough=True)
+            return z
+        return xnn.bottleneck_tail(self.conv3, self.bn3, out, self.downsample[0], self.downsample[1], x)
 
 
 class _Pool(nn.Module):
@@ -169,10 +170,12 @@ class StBottleneck(nn.Module):
                 ops.carry_amax(x, pooled)
             else:
                 pooled = ops.carry_amax(x, ops.AvgPoolFn.apply(x, k, k, 0, True, False))
+            # the shortcut's BatchNorm runs inside conv3's BatchNorm passes (xnn.bottleneck_tail)
             if want and k == 1:
-                idt, self.alias_out = xnn.conv_bn_act(self.downsample[1], self.downsample[2], pooled, passthrough=True)
-            else:
-                idt = xnn.conv_bn_act(self.downsample[1], self.downsample[2], pooled)
+                z, self.alias_out = xnn.bottleneck_tail(self.conv3, self.bn3, out, self.downsample[1], self.downsample[2], pooled,
+                                                        passthrough=True)
+                return z
+            return xnn.bottleneck_tail(self.conv3, self.bn3, out, self.downsample[1], self.downsample[2], pooled)
         return xnn.conv_bn_act(self.conv3, self.bn3, out, act=ops.ACT_RELU, residual=idt)
 
 

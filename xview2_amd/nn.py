@@ -96,6 +96,29 @@ def conv_bn_act_head(conv, bn, head, x0, x1=None, act=ops.ACT_NONE, nchw_out=Tru
                                      head._parameters["bias"], cfg, bs, act, nchw_out)
 
 
+def bottleneck_tail(conv3, bn3, out, conv_ds, bn_ds, x, act=ops.ACT_RELU, passthrough=False):
+    """act(BN3(conv3(out)) + BN_ds(conv_ds(x))): the tail of a bottleneck block with a projection shortcut.  One autograd node
+    that stores neither the shortcut's normalised output nor the residual gradient (ops.BottleneckTailFn) where
+    ops.shortcut_fusable() allows it and nothing watches the layers from outside, else the two conv_bn_act nodes it replaces.
+    passthrough=True returns (z, alias of x) like conv_bn_act(conv_ds, bn_ds, x, passthrough=True)."""
+    cfg3, cfgd = _cfg(conv3), _cfg(conv_ds)
+    bs3, bsd = ops.BnState(bn3, SYNC_BN), ops.BnState(bn_ds, SYNC_BN)
+    w3, wd = conv3._parameters["weight"], conv_ds._parameters["weight"]
+    if (not ops.shortcut_fusable(out, x, w3, cfg3, bs3, wd, cfgd, bsd, act, bn3.training and bn_ds.training)
+            or observed(conv3, bn3, conv_ds, bn_ds)):
+        if passthrough:
+            idt, alias = conv_bn_act(conv_ds, bn_ds, x, passthrough=True)
+            return conv_bn_act(conv3, bn3, out, act=act, residual=idt), alias
+        return conv_bn_act(conv3, bn3, out, act=act, residual=conv_bn_act(conv_ds, bn_ds, x))
+    bump_bn_counter(bn_ds)
+    bump_bn_counter(bn3)
+    res = ops.BottleneckTailFn.apply(out, x, w3, bs3.weight, bs3.bias, wd, bsd.weight, bsd.bias, cfg3, cfgd, bs3, bsd, act,
+                                     bool(passthrough))
+    if passthrough:
+        ops.carry_amax(x, res[1])
+    return res
+
+
 def observed(*mods):
     """does anything watch these modules (or their children) from outside - a forward (pre-)hook, on them or global?  Such a module's
     inputs and outputs have a consumer the graph does not show."""

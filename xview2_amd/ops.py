@@ -1424,6 +1424,144 @@ class ConvBnActHeadFn(torch.autograd.Function):
                 dhw.reshape(ctx.hshape), dhb, None, None, None, None)
 
 
+SHORTCUT_FUSE = os.environ.get("XV2_SHORTCUT_FUSE", "1") != "0"      # the projection shortcut's BatchNorm inside conv3's BatchNorm passes (include/xv2.h)
+
+
+def shortcut_fusable(a, x, w3, g3, bn3, w_ds, g_ds, bn_ds, act, training):
+    """Can act(BN3(conv3(a)) + BN_ds(conv_ds(x))) run as BottleneckTailFn?  Training mode with gradients, one BatchNorm batch in
+    one process (no BN_SPLIT, no SyncBatchNorm exchange), two ungrouped convolutions whose statistics fold inside their launch,
+    and a shape the fused kernels take (xv2_bn_act_shortcut_supported)."""
+    if not (SHORTCUT_FUSE and training and torch.is_grad_enabled() and BN_SPLIT == 1 and a.is_cuda and x.is_cuda):
+        return False
+    if act not in (ACT_RELU, ACT_LEAKY) or g3.groups != 1 or g_ds.groups != 1 or a.dtype != x.dtype or a.dim() != 4 or x.dim() != 4:
+        return False
+    for bn in (bn3, bn_ds):
+        if _sync_group(bn) or bn.weight is None or bn.bias is None or bn.running_mean is None or bn.running_var is None:
+            return False
+    if a.shape[3] == 4 or x.shape[3] == 4:      # (the RGB stem's image is no block input)
+        return False
+    N, IH, IW, Ca = a.shape
+    OH, OW = _out_hw(IH, IW, g3)
+    C = w3.shape[0]
+    if w_ds.shape[0] != C or x.shape[0] != N or _out_hw(x.shape[1], x.shape[2], g_ds) != (OH, OW):
+        return False
+    half = a.dtype == torch.bfloat16
+    if query("xv2_bn_act_shortcut_supported", N * OH * OW, C, XV2_BF16 if half else XV2_F32) != 1:
+        return False
+    d3 = _desc(N, IH, IW, Ca, 0, C, g3, OH, OW, half)
+    dd = _desc(N, x.shape[1], x.shape[2], x.shape[3], 0, C, g_ds, OH, OW, half)
+    return query("xv2_conv2d_forward_stats_tiles", d3) > 0 and query("xv2_conv2d_forward_stats_tiles", dd) > 0
+
+
+class BottleneckTailFn(torch.autograd.Function):
+    """z = act(BN3(conv3(a)) + BN_ds(conv_ds(x))): the last convolution of a bottleneck block and its projection shortcut
+    (torchvision Bottleneck.forward / ResNeSt Bottleneck.forward: `out = bn3(conv3(out)); out += downsample(x); relu`) as ONE
+    autograd node.  The shortcut's normalised output and the residual gradient are never stored: one apply pass reads both raw
+    convolution outputs, one column pass and one apply pass serve both BatchNorms in backward (xv2_bn_act_shortcut_forward /
+    _backward).  Bit-identical to the two ConvBnActFn nodes it replaces.  Callers check shortcut_fusable() first."""
+
+    @staticmethod
+    def forward(ctx, a, x, w3, gamma3, beta3, w_ds, gamma_ds, beta_ds, g3, g_ds, bn3, bn_ds, act, passthrough=False):
+        """passthrough: also return x itself as a second output (ConvBnActFn.forward: the alias a further consumer of the block
+        input reads; its gradient is summed inside the shortcut convolution's backward-data epilogue)"""
+        _need_cuda(a)
+        ctx.set_materialize_grads(False)
+        ctx.passthrough = bool(passthrough)
+        a_in, x_in = a, x
+        a, x = a.contiguous(), x.contiguous()
+        ctx.ihwo3 = [] if a.requires_grad else None
+        ctx.ihwod = [] if x.requires_grad else None
+        am_a = am_x = am_out = None
+        active = _amax_active(a)
+        if active:      # F16X2: the sources' maxima and a slot for z
+            am_a, am_x = getattr(a_in, "_xv2_amax", None), getattr(x_in, "_xv2_amax", None)
+            am_out = _amax_new(a)
+        ctx.am_in = (am_a, am_x) if active else None
+        ctx.want_dx_amax = (active and bool(getattr(a_in, "_xv2_convT_out", False)),
+                            active and bool(getattr(x_in, "_xv2_convT_out", False)))
+        # the shortcut first, like the two nodes: convolution + statistics + coefficients each, no apply pass
+        yd, sums_d, cd = _conv_forward(x, None, w_ds, g_ds, None, want_stats=True, ihwo_out=ctx.ihwod, bn=bn_ds,
+                                       amax_in=(_tok_ptr(am_x), None) if active else None)
+        y3, sums_3, c3 = _conv_forward(a, None, w3, g3, None, want_stats=True, ihwo_out=ctx.ihwo3, bn=bn3,
+                                       amax_in=(_tok_ptr(am_a), None) if active else None)
+        if cd is None or c3 is None or yd.shape != y3.shape:
+            raise RuntimeError("BottleneckTailFn: the statistics did not fold inside the convolution (shortcut_fusable() decides "
+                               "before the node is built)")
+        N, OH, OW, C = y3.shape
+        npix = N * OH * OW
+        z = torch.empty_like(y3)
+        zmask = torch.empty((npix * (C // 4),), dtype=torch.uint8, device=y3.device)
+        if am_out is not None:      # the apply pass records max |z|
+            set_amax(None, None, None, am_out[0])
+            z._xv2_amax = am_out
+        call("xv2_bn_act_shortcut_forward", y3, yd, c3[2], c3[3], cd[2], cd[3], act, z, zmask, npix, C, _dt(y3))
+        ctx.save_for_backward(a, x, w3, w_ds, gamma3, gamma_ds, y3, yd, zmask, c3[0], c3[1], cd[0], cd[1])
+        ctx.count, ctx.g3, ctx.g_ds, ctx.bn3, ctx.bn_ds, ctx.act = float(npix), g3, g_ds, bn3, bn_ds, act
+        ctx.wparams = (w3, w_ds)
+        return (z, x_in) if ctx.passthrough else z
+
+    @staticmethod
+    def backward(ctx, dz, dpass=None):
+        a, x, w3, w_ds, gamma3, gamma_ds, y3, yd, zmask, mean3, invstd3, meand, invstdd = ctx.saved_tensors
+        N, OH, OW, C = y3.shape
+        npix = N * OH * OW
+        if dz is None:
+            dz = torch.zeros_like(y3)
+        dz = _same(dz, y3).contiguous()
+        dpass = _same(dpass, y3)
+        bn3, bn_ds = ctx.bn3, ctx.bn_ds
+        sums2 = torch.empty((2 * C, 2), dtype=torch.float64, device=y3.device)
+        dgamma3, dbeta3 = _grad_like(bn3.weight), _grad_like(bn3.bias)
+        dgammad, dbetad = _grad_like(bn_ds.weight), _grad_like(bn_ds.bias)
+        ws = _persist("bnshortcut", (query("xv2_bn_act_shortcut_backward_workspace", npix, C) + 3) // 4 + 4, y3.device)
+        dy3, dyd = torch.empty_like(y3), torch.empty_like(yd)
+        am_in = ctx.am_in
+        tok3 = tokd = None
+        if am_in is not None:        # F16X2: the apply pass records max |dy3| and max |dy_ds|
+            tok3, tokd = _amax_new(y3), _amax_new(y3)
+            if tok3 is not None:
+                set_amax(None, None, None, tok3[0])
+                dy3._xv2_amax = tok3
+            if tokd is not None:
+                dyd._xv2_amax = tokd
+        call("xv2_bn_act_shortcut_backward", dz, zmask, y3, yd, mean3, invstd3, gamma3, meand, invstdd, gamma_ds, ctx.act,
+             ctx.count, dy3, dyd, npix, C, sums2, dgamma3, dbeta3, dgammad, dbetad, tokd[0] if tokd is not None else None, ws,
+             _dt(y3))
+        w3p, wdp = ctx.wparams
+        ctx.wparams = None
+        need = ctx.needs_input_grad
+        # conv3's gradients, then the shortcut convolution's - the order of the two nodes
+        da, dw3 = _tail_conv_grads(a, w3, ctx.g3, dy3, ctx.ihwo3, None, am_in[0] if am_in is not None else None,
+                                   ctx.want_dx_amax[0], need[0], need[2], w3p)
+        dx, dwd = _tail_conv_grads(x, w_ds, ctx.g_ds, dyd, ctx.ihwod, dpass, am_in[1] if am_in is not None else None,
+                                   ctx.want_dx_amax[1], need[1], need[5], wdp)
+        ctx.ihwo3 = ctx.ihwod = None
+        return (da, dx, dw3, dgamma3 if need[3] else None, dbeta3 if need[4] else None, dwd, dgammad if need[6] else None,
+                dbetad if need[7] else None, None, None, None, None, None, None)
+
+
+def _tail_conv_grads(x0, weight, g, dy, ihwo, dpass, am_x0, want_dx_amax, need_dx, need_dw, wparam):
+    """input and weight gradient of one single-source convolution of BottleneckTailFn, the way ConvBnActFn.backward takes them:
+    `dpass` (the gradient of the pass-through alias) is summed inside the backward-data epilogue where its layout allows"""
+    am_dy = _amax_ptr(dy)
+    dx0 = None
+    if need_dx:
+        acc = None
+        if dpass is not None and dpass.is_contiguous() and tuple(dpass.shape) == tuple(x0.shape):
+            acc, dpass = dpass, None
+        dx0, _ = _conv_backward_data(dy, weight, g, x0.shape[:3], x0.shape[3], 0, ihwo, acc, None, am_dy,
+                                     _amax_new(dy) if (want_dx_amax and am_dy is not None and dpass is None) else None)
+        if dpass is not None:
+            dx0 = dx0 + dpass
+    elif dpass is not None:
+        dx0 = dpass
+    dw = None
+    if need_dw:
+        wam = (_tok_ptr(am_x0), None, am_dy) if am_dy is not None else None
+        dw = _conv_backward_weight(x0, None, dy, weight, g, wparam, wam)
+    return dx0, dw
+
+
 class ConvFn(torch.autograd.Function):
     """y = conv(cat(x0, x1), W) + bias (no normalisation)"""
 
