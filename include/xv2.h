@@ -920,6 +920,39 @@ int xv2_polygon_count(const int32_t* labels, int B, int H, int W, void* workspac
 int xv2_polygon_trace(const int32_t* labels, int B, int H, int W, int64_t total_edges, int64_t total_vertices,
                       void* workspace, int64_t* rings, int32_t* verts, int32_t* ring_count, int32_t* status, void* stream);
 
+/* ---- polygons -> masks (rasterize.hip, xview2_amd/utils/rasterize.py): the inverse of the outlines above ----------------------
+ * Coordinates.  Vertices are int32 in units of 2^-k pixel, k = frac_bits in 0..8.  Pixel (y,x) is sampled at the point
+ * s = ((x << k) + off, (y << k) + off).  off = 0 samples the lattice point (a vertex is a pixel index, the convention of the
+ * reference's label conversion); off = 2^(k-1), k >= 1, samples the pixel centre (the convention of the outlines, where pixel
+ * (y,x) covers [x,x+1] x [y,y+1]).  |coordinate| <= 2^24 and max(H, W) << k <= 2^24, so every cross product fits int64 with
+ * room to spare.
+ * Coverage of one feature.  A feature is a set of rings, flattened by the host into directed edges a -> b.  With
+ * cr = (bx - ax)(sy - ay) - (by - ay)(sx - ax) in int64: s is ON the edge if cr == 0 and s lies in the edge's closed box; the
+ * edge is CROSSED if min(ay, by) <= sy < max(ay, by) and the edge's x at height sy is greater than sx, that is cr > 0 when
+ * by > ay and cr < 0 otherwise (horizontal edges never cross).  The pixel is covered iff it is on some edge or an odd number
+ * of edges cross: even-odd over all rings with a closed boundary.  Holes are rings like any other, orientation does not
+ * matter, and a zero-area feature covers exactly the sample points on its edges.
+ * Painting.  Features of a tile are painted in table order and the last one wins: out[b][y][x] (uint8 [B,H,W]) is the value
+ * of the last covering feature, or 0 if none.
+ * Tables.  One int32 buffer, uploaded once; the call takes its device copy and its host copy (as xv2_autoaugment_u8 takes its
+ * decisions).  Its parts, in order:
+ *   edges     [n_edges][4]     ax, ay, bx, by
+ *   features  [n_features][8]  tile, value 0..255, first edge, edge count, clipped pixel box x0, y0, x1, y1 (inclusive);
+ *                              sorted by tile, file order inside a tile
+ *   work      [n_work][4]      feature, window x0, window y0, 0: one 32 x 32 window of the feature's box; pixels of a window
+ *                              beyond the box are not painted, pixels of the box that no window holds stay unpainted
+ * The host copy is validated before anything is enqueued: index ranges, boxes inside the tile, window origins inside their
+ * boxes, tile order, value range, coordinate bounds, frac_bits and off.  A failure returns XV2_EINVAL and nothing is written.
+ * n_features == 0 or n_work == 0 is valid and gives an all-zero out (the tables may then be NULL when all three counts are 0).
+ * The device tables and the workspace must be 16-byte aligned, out 4-byte aligned.  Size limits as xv2_postprocess
+ * (H * W < 2^30, B <= 65535); the workspace query (4 bytes per pixel, cleared by the call itself) is 0 outside them.  Three
+ * launches (clear, cover, resolve), nothing is read back, every value is an integer and the only atomic is an integer max:
+ * the same bits come out of every run. */
+size_t xv2_rasterize_workspace(int B, int H, int W);
+int xv2_rasterize_polygons(const int32_t* dev_tables, const int32_t* host_tables, int64_t n_edges, int n_features,
+                           int64_t n_work, int frac_bits, int off, int B, int H, int W, void* workspace, uint8_t* out,
+                           void* stream);
+
 /* ---- scene inference: windows of a scene of any size, blended on the device (xview2_amd/scene.py, scene.hip) ---------
  * A scene is H x W pixels, H * W < 2^30.  Windows are h x w (multiples of 32, 32..2048) with their origins (y0, x0) in a
  * device table; the table's order is the summation order.  tri(i, L) is reflection without repeating the edge, iterated:

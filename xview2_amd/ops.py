@@ -2575,3 +2575,30 @@ def polygon_trace(labels, total_edges, total_vertices):
         raise RuntimeError("polygon_trace: the label map has other totals than %d edges and %d vertices; pass the sums of "
                            "polygon_count of the same labels" % (E, V))
     return rings, verts, ring_count
+
+
+def rasterize_polygons(tables, n_edges, n_features, n_work, frac_bits, off, B, H, W, device=None):
+    """Polygons -> a painted uint8 [B,H,W] map on the device (include/xv2.h xv2_rasterize_polygons).  tables: the int32 numpy
+    buffer of utils.rasterize.pack (edges, features, work items); it is uploaded once here and its host copy is what the
+    entry point validates.  Tables the entry point rejects raise RuntimeError with its message."""
+    import numpy as np
+    if not torch.cuda.is_available():
+        raise RuntimeError("xview2_amd ops run on the MI355X only; there is no CPU fallback")
+    host = np.ascontiguousarray(tables)
+    if host.dtype != np.int32 or host.ndim != 1:
+        raise ValueError("rasterize_polygons: tables must be a flat int32 numpy array, got %s %s" % (host.dtype, host.shape))
+    E, F, K = int(n_edges), int(n_features), int(n_work)
+    if min(E, F, K) < 0 or host.size != 4 * E + 8 * F + 4 * K:
+        raise ValueError("rasterize_polygons: %d table words do not hold %d edges, %d features and %d work items"
+                         % (host.size, E, F, K))
+    B, H, W = int(B), int(H), int(W)
+    need = int(query("xv2_rasterize_workspace", B, H, W))
+    if need == 0:
+        raise ValueError("rasterize_polygons: B=%d H=%d W=%d outside the supported sizes (H*W < 2^30, B <= 65535)" % (B, H, W))
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    out = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
+    ws = _ws(need, out)
+    buf = torch.from_numpy(host).to(dev) if host.size else None        # (host stays alive until the call returns)
+    call("xv2_rasterize_polygons", buf, host.ctypes.data if host.size else None, E, F, K, int(frac_bits), int(off), B, H, W,
+         ws, out)
+    return out
