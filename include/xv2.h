@@ -68,10 +68,11 @@ typedef struct xv2_conv_desc {
  * mode the host layer uses for fp32 tensors by default (XV2_F32X3=0 in the environment selects XV2_MATH_F32).
  * NON-FINITE OPERANDS: the split of +-Inf is h = Inf, m = bf16(Inf - Inf) = NaN, so an operand element that is +-Inf (or NaN)
  * makes every output it contributes to NaN, where the exact-fp32 MFMA (and torch) would propagate +-Inf through products
- * with non-zero finite values.  Both are already-diverged training states; finite inputs are unaffected (every finite fp32
- * splits exactly, including denormals and values whose bf16 rounding overflows to Inf: bf16 has fp32's exponent range, a
- * finite fp32 rounds to a finite bf16 or to Inf only above 0x7f7f8000 ~ 3.39e38, where h = Inf again yields NaN).  Callers
- * that must keep Inf semantics select XV2_MATH_F32. */
+ * with non-zero finite values.  Both are already-diverged training states; finite inputs are unaffected: bf16 has fp32's exponent
+ * range, so a finite fp32 rounds to a finite h (to Inf only above 0x7f7f8000 ~ 3.39e38, where h = Inf again yields NaN), and
+ * the three terms add up to x exactly whenever x is a multiple of 2^-133, the smallest bf16 denormal - every x with
+ * |x| >= 2^-110, and the smaller ones whose low bits are zero; the rest (denormals, the smallest normals) lose what lies
+ * below 2^-133, at most 2^-134 (tests/test_weights_ref_cpu.py).  Callers that must keep Inf semantics select XV2_MATH_F32. */
 #define XV2_MATH_F32X3 3
 
 /* element type of activation tensors for the non-convolution entry points (`dtype` arguments) */

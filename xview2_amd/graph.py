@@ -42,6 +42,10 @@ class GraphedStep:
         finally:
             ops.amax_end_capture(self._amax)
             xnn.bump_bn_counter = orig
+        # the captured weight refresh (ops.repack_all) names its tables, the arena of the weights' maxima and every cached layout and
+        # plane buffer by address; the pack cache drops them whenever a layer is packed for the first time, evicted or the cache is
+        # cleared - the graph keeps what it names, so that a later replay never touches released memory
+        self._refresh_keep = ops.refresh_named_tensors()
         # capture records the launches WITHOUT executing them: undo the host-side bookkeeping of that pass
         optimizer.step_count -= 1
         for bn in self._bumped:

@@ -518,6 +518,25 @@ def repack_all():
         e.version, e.epoch = e.w._version, WEIGHT_EPOCH
 
 
+def refresh_named_tensors():
+    """every tensor whose address the launches of repack_all() carry right now: the device tables, the arena of the weights' maxima,
+    and each cached entry's source view, packed layouts and plane buffers.  A captured training step records those launches with
+    raw addresses and replays them for as long as it lives, while nothing but this module's globals keeps the memory allocated -
+    the next table rebuild (_invalidate_pack_table), an eviction or clear_pack_cache() drops it.  graph.GraphedStep therefore
+    keeps this list for its lifetime."""
+    keep = []
+    if _pack_table is not None:
+        table, _, _, xt, at, ht = _pack_table
+        keep.append(table)
+        keep.extend(t[0] for t in (xt, at, ht) if t is not None)
+    keep.extend(a[0] for a in _wamax.values())
+    for e in _packs.values():
+        keep.extend(t for t in (e.w, e.ohwi, e.ihwo) if t is not None)
+        keep.extend((e.x3 or {}).values())
+        keep.extend(v[0] for v in (e.x2 or {}).values())
+    return keep
+
+
 def clear_pack_cache():
     global _pack_table
     for k in list(_packs):
