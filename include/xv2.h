@@ -881,6 +881,52 @@ size_t xv2_building_table_workspace(int B, int H, int W);
 int xv2_building_table(const int32_t* labels, const uint8_t* dmg, const float* loc, int B, int H, int W, int max_rows,
                        void* workspace, int64_t* rows, int32_t* count, void* stream);
 
+/* ---- predicted buildings matched to labelled buildings by IoU (match.hip, xview2_amd/utils/building_metrics.py) -------
+ * labels_*: int32 [B,H,W] as xv2_label_components writes them; rows_*: int64 [B][max_rows_*][16] and count_*: int32 [B] as
+ * xv2_building_table wrote them for those labels.  p is the prediction, t the target; the entry is symmetric in them.
+ * match_p: int64 [B][max_rows_p][8], match_t likewise with max_rows_t; rows 0 .. min(count[b], max_rows) - 1 of a tile are
+ * written, in the table's row order; nothing else of the buffers is touched.  Columns of the row of building a, where b
+ * ranges over the buildings of the other map that share at least one pixel with it, I(a,b) = |a n b| and
+ * U(a,b) = |a| + |b| - I (areas: column 1 of the tables):
+ *   0        row index of the best partner in the other table, -1 if there is none: the largest I / U, fractions compared
+ *            exactly (I1 * U2 vs I2 * U1 in int64), ties to the partner with the smaller column-0 root
+ *   1        I with that partner (0 if none)
+ *   2        U with that partner (the building's own area if none)
+ *   3        1 if matched, else 0: the partner's best partner is this building (mutual best) AND I * iou_den >= iou_num * U
+ *   4        the number of distinct partners: 0 is a missed or spurious building, more than 1 a merge or a split
+ *   5..7     0
+ * Threshold.  1 <= iou_num <= iou_den <= 65536 and 2 * iou_num >= iou_den, anything else is XV2_EINVAL.  With a threshold of
+ * at least 1/2 a pair that passes has I >= U / 2 and U >= max(|a|, |b|), so it holds at least half of both areas and more
+ * than half of both as soon as I / U > 1/2; partners of one building are disjoint, so no building has two partners above
+ * 1/2: the matched set is the same under every matching rule in use (greedy by score, Hungarian, mutual best) and no
+ * ordering of the predictions enters.  (Two passing partners at I / U = 1/2 exactly would each be half of the building, lie
+ * inside it and tile it, so they would touch and be one component: with tables that are the labels' own, a pair that passes
+ * is always mutual.  The mutual test decides only when a table comes from another map; the tie rule of column 0 then picks
+ * one.)  Thresholds below 1/2 are rejected rather than given a made-up rule.
+ * Pieces.  The 4-connected components of the overlap mask (labels_p != 0) & (labels_t != 0) each lie inside one pair (two
+ * 4-adjacent foreground pixels of a map share its component), a pair may own several, and I is the sum of their areas.
+ * piece_count[b] (int32 [B], overwritten by every call) is the true number of pieces of tile b, even above max_pieces.  A
+ * tile's match rows are valid when piece_count[b] <= max_pieces, count_p[b] <= max_rows_p and count_t[b] <= max_rows_t;
+ * otherwise that tile's rows hold unspecified values inside their own storage, and the other tiles are unaffected.
+ * No input that passes the host-side argument checks makes a kernel address outside its buffers: a label that names no row
+ * of its table is dropped (its root label - 1 must be column 0 of a row below min(count, max_rows), found by bisection over
+ * the ascending column 0, so no per-pixel rank map and no uninitialised word is read); a row whose column 0 is outside
+ * 0 .. H*W-1 or whose area is outside 1 .. H*W is dropped; pieces of rank >= max_pieces are not inserted, so the pair
+ * table, sized for max_pieces entries at load factor at most 1/2, can never fill; every probe and retry loop has a bound.
+ * Built as: overlap mask, xv2_label_components and xv2_building_table on it (piece_count; root and area per piece), pair
+ * table cleared and match rows initialised in one launch, one thread per piece inserting (rank_p, rank_t) with a 64-bit compare-and-swap and
+ * adding its area, one thread per pair offering (I, partner) to both buildings' best-partner words, one thread per building
+ * resolving, one pass returning the scratch column to 0: fourteen launches whatever B, H, W and content, nothing read back.
+ * Every reduction is an integer add or an exact compare-and-swap towards the maximum of a total order: the same input gives
+ * the same bytes on every run.  Size limits as xv2_postprocess (H * W < 2^30, B <= 65535), max_rows_* >= 1, max_pieces >= 1;
+ * the workspace query is 0 outside them; the workspace needs no clearing. */
+#define XV2_MATCH_COLS 8
+size_t xv2_building_match_workspace(int B, int H, int W, int max_pieces);
+int xv2_building_match(const int32_t* labels_p, const int64_t* rows_p, const int32_t* count_p, int max_rows_p,
+                       const int32_t* labels_t, const int64_t* rows_t, const int32_t* count_t, int max_rows_t,
+                       int B, int H, int W, int iou_num, int iou_den, int max_pieces, void* workspace,
+                       int64_t* match_p, int64_t* match_t, int32_t* piece_count, void* stream);
+
 /* ---- building outlines of a label map (polygons.hip, xview2_amd/utils/polygons.py) ------------------------------------
  * Input and grid.  labels: int32 [B,H,W] as xv2_label_components writes them.  A pixel is foreground if it is inside the
  * tile and its label is not 0.  Pixel (y,x) covers the square [x,x+1] x [y,y+1]; corners are the lattice points (x,y) with

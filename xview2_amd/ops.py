@@ -2549,6 +2549,54 @@ def building_table(labels, dmg, loc=None, max_rows=None):
     return rows, count
 
 
+# ---- predicted buildings matched to labelled buildings (csrc/match.hip) ---------------------------------------------------
+MATCH_COLS = 8
+
+
+def building_match(labels_p, rows_p, count_p, labels_t, rows_t, count_t, iou=(1, 2), max_pieces=None):
+    """Best partner, I, U, matched flag and partner count of every building of two tables (include/xv2.h
+    xv2_building_match).  labels_*: int32 [B,H,W]; rows_*: int64 [B, max_rows_*, 16] and count_*: int32 [B] as building_table
+    returned them for those labels.  iou: (num, den) with 1 <= num <= den <= 65536 and 2 * num >= den.  max_pieces: capacity
+    of overlap pieces per tile (default max(1024, H*W // 256)).  Returns (match_p int64 [B, max_rows_p, 8], match_t int64
+    [B, max_rows_t, 8], piece_count int32 [B]) on the device; only rows 0 .. min(count[b], max_rows) - 1 of a tile are
+    written, and a tile is valid when piece_count[b] <= max_pieces and neither count exceeds its max_rows."""
+    for t in (labels_p, rows_p, count_p, labels_t, rows_t, count_t):
+        _need_cuda(t)
+    if labels_p.dim() != 3 or labels_p.dtype != torch.int32:
+        raise ValueError("building_match: labels_p must be int32 [B,H,W], got %s %s" % (labels_p.dtype, tuple(labels_p.shape)))
+    if labels_t.dtype != torch.int32 or labels_t.shape != labels_p.shape:
+        raise ValueError("building_match: labels_t must be int32 %s, got %s %s" % (tuple(labels_p.shape), labels_t.dtype,
+                                                                                  tuple(labels_t.shape)))
+    B, H, W = (int(v) for v in labels_p.shape)
+    for name, rows, count in (("p", rows_p, count_p), ("t", rows_t, count_t)):
+        if rows.dtype != torch.int64 or rows.dim() != 3 or rows.shape[0] != B or rows.shape[1] < 1 or rows.shape[2] != BUILDING_COLS:
+            raise ValueError("building_match: rows_%s must be int64 [%d, max_rows >= 1, %d], got %s %s"
+                             % (name, B, BUILDING_COLS, rows.dtype, tuple(rows.shape)))
+        if count.dtype != torch.int32 or tuple(count.shape) != (B,):
+            raise ValueError("building_match: count_%s must be int32 [%d], got %s %s" % (name, B, count.dtype, tuple(count.shape)))
+    dev = labels_p.device
+    if any(t.device != dev for t in (rows_p, count_p, labels_t, rows_t, count_t)):
+        raise ValueError("building_match: all six tensors must be on %s" % (dev,))
+    num, den = (int(v) for v in iou)
+    if not (1 <= num <= den <= 65536 and 2 * num >= den):
+        raise ValueError("building_match: iou=%d/%d must satisfy 1 <= num <= den <= 65536 and num/den >= 1/2" % (num, den))
+    max_pieces = max(1024, H * W // 256) if max_pieces is None else int(max_pieces)
+    if max_pieces < 1:
+        raise ValueError("building_match: max_pieces must be at least 1, got %d" % max_pieces)
+    need = int(query("xv2_building_match_workspace", B, H, W, max_pieces))
+    if need == 0:
+        raise ValueError("building_match: B=%d H=%d W=%d outside the supported sizes (H*W < 2^30, B <= 65535)" % (B, H, W))
+    labels_p, rows_p, count_p = labels_p.contiguous(), rows_p.contiguous(), count_p.contiguous()
+    labels_t, rows_t, count_t = labels_t.contiguous(), rows_t.contiguous(), count_t.contiguous()
+    ws = _ws(need, labels_p)
+    match_p = torch.empty((B, rows_p.shape[1], MATCH_COLS), dtype=torch.int64, device=dev)
+    match_t = torch.empty((B, rows_t.shape[1], MATCH_COLS), dtype=torch.int64, device=dev)
+    piece_count = torch.empty((B,), dtype=torch.int32, device=dev)
+    call("xv2_building_match", labels_p, rows_p, count_p, int(rows_p.shape[1]), labels_t, rows_t, count_t, int(rows_t.shape[1]),
+         B, H, W, num, den, max_pieces, ws, match_p, match_t, piece_count)
+    return match_p, match_t, piece_count
+
+
 # ---- building outlines of a label map (csrc/polygons.hip) ----------------------------------------------------------------
 POLYGON_RING_COLS = 8
 
