@@ -1000,6 +1000,49 @@ int xv2_rasterize_polygons(const int32_t* dev_tables, const int32_t* host_tables
                            int64_t n_work, int frac_bits, int off, int B, int H, int W, void* workspace, uint8_t* out,
                            void* stream);
 
+/* ---- split touching buildings (split.hip, xview2_amd/utils/split.py) -------------------------------------------------------
+ * Per tile, mask is uint8 [H,W], M = mask != 0, and r2 >= 1 is an integer squared radius.  Neighbours are 4-neighbours inside
+ * the tile.
+ * Distance.  cap = floor(sqrt(r2)) + 1 and d2(p) = min(cap^2, min over q in the tile with !M(q) of |p - q|^2).  Pixels
+ * outside the tile are not background: a building cut by the tile edge is not eroded from that edge, and an all-ones tile has
+ * d2 = cap^2 everywhere.  d2 is exact wherever it is below cap^2.
+ * Seeds.  S = M & (d2 > r2); a seed's label is the one xv2_label_components(S) gives it: 1 + the smallest linear index of its
+ * 4-connected component.
+ * Growth.  For a pixel p of M, g_l(p) is the 4-connected geodesic distance inside M from p to the seed labelled l,
+ * g(p) = min over l of g_l(p), and L(p) = min{ l : g_l(p) = g(p) }; L(p) = 0 for background and for pixels of components of M
+ * that hold no seed.  Equivalently L is the fixed point of synchronous rounds in which every unlabelled pixel of M with a
+ * labelled neighbour takes the smallest label among those neighbours, and the unique fixed point of relaxing the key (g, l),
+ * ordered lexicographically, with key(p) <- min(key(p), key(q) + (1, 0)) over the neighbours q in M, in any order of
+ * relaxations: the kernel's schedule does not enter the result.
+ * Cut.  p is cut iff L(p) > 0 and some neighbour q has 0 < L(q) < L(p).  out = M & !cut as uint8 with the input's own values
+ * kept: out(p) = mask(p) or 0.
+ * So out <= mask; every component of out lies inside one component of mask and carries one value of L; two pixels with
+ * different non-zero L are never adjacent in out; a component of mask with at most one seed is returned untouched (thin or
+ * small buildings that the erosion removes entirely stay as they are); a straight neck of width n between two wide bodies is
+ * cut iff ceil(n / 2)^2 <= r2.
+ * xv2_edt_sq: d2 as uint16 [B,H,W] for 1 <= cap <= 64, one launch.
+ * xv2_split_seed: the distance, the threshold, xv2_label_components on the seeds and the growth state: seeds (0, label), other
+ * mask pixels (inf, 0); five launches.
+ * xv2_split_grow: sweeps >= 1 sweeps, one launch each.  In a sweep every block loads its 64 x 64 region of keys plus a 1-pixel
+ * ring from one buffer, relaxes inside LDS until the region is stable against that ring (a bounded loop), and writes the region
+ * to the other buffer; the buffers swap every sweep, so no block reads what another writes and the state after s sweeps is a
+ * function of the input alone.  A region that changed neither in this sweep nor in the one before is read and not written,
+ * and a region that rested in the previous sweep together with its four neighbouring regions is not even read.
+ * The state is left in the first buffer: an odd number of sweeps ends with a copy, an even one does not.  *pending (device
+ * int32, overwritten by the call) is non-zero iff the last sweep changed anything: the host reads it once per call and stops
+ * at 0, the only read-back.
+ * xv2_split_finish: the cut; out uint8 [B,H,W], and L as int32 [B,H,W] into labels unless it is NULL.  L carries seed labels;
+ * it is no component labelling of out.
+ * The three calls take the same mask, sizes and workspace.  Size limits as xv2_postprocess (H * W < 2^30, B <= 65535), r2 in
+ * 1..4095; the workspace query (16 bytes per pixel and 8 per region) is 0 outside the limits.  The workspace must be 16-byte
+ * aligned and needs no clearing.  No input is written, nothing is written outside out, labels, d2, pending and the workspace,
+ * and a bad argument is XV2_EINVAL before anything is enqueued. */
+int xv2_edt_sq(const uint8_t* mask, int B, int H, int W, int cap, uint16_t* d2, void* stream);
+size_t xv2_split_workspace(int B, int H, int W);
+int xv2_split_seed(const uint8_t* mask, int B, int H, int W, int r2, void* workspace, void* stream);
+int xv2_split_grow(const uint8_t* mask, int B, int H, int W, int sweeps, void* workspace, int32_t* pending, void* stream);
+int xv2_split_finish(const uint8_t* mask, int B, int H, int W, void* workspace, uint8_t* out, int32_t* labels, void* stream);
+
 /* ---- scene inference: windows of a scene of any size, blended on the device (xview2_amd/scene.py, scene.hip) ---------
  * A scene is H x W pixels, H * W < 2^30.  Windows are h x w (multiples of 32, 32..2048) with their origins (y0, x0) in a
  * device table; the table's order is the summation order.  tri(i, L) is reflection without repeating the edge, iterated:

@@ -2669,3 +2669,53 @@ def rasterize_polygons(tables, n_edges, n_features, n_work, frac_bits, off, B, H
     call("xv2_rasterize_polygons", buf, host.ctypes.data if host.size else None, E, F, K, int(frac_bits), int(off), B, H, W,
          ws, out)
     return out
+
+
+# ---- split touching buildings (csrc/split.hip) ---------------------------------------------------------------------------
+def _split_mask(what, mask):
+    _need_cuda(mask)
+    if mask.dim() != 3 or mask.dtype not in (torch.uint8, torch.bool):
+        raise ValueError("%s: mask must be uint8 [B,H,W], got %s %s" % (what, mask.dtype, tuple(mask.shape)))
+    B, H, W = (int(v) for v in mask.shape)
+    if int(query("xv2_split_workspace", B, H, W)) == 0:
+        raise ValueError("%s: B=%d H=%d W=%d outside the supported sizes (H*W < 2^30, B <= 65535)" % (what, B, H, W))
+    return mask.to(torch.uint8).contiguous(), B, H, W
+
+
+def edt_sq(mask, cap):
+    """Capped exact squared distance to the nearest background pixel of the tile (include/xv2.h xv2_edt_sq): mask uint8
+    [B,H,W], 1 <= cap <= 64.  Returns uint16 [B,H,W] = min(cap^2, d^2) on the device; pixels outside the tile are no
+    background."""
+    mask, B, H, W = _split_mask("edt_sq", mask)
+    cap = int(cap)
+    if not 1 <= cap <= 64:
+        raise ValueError("edt_sq: cap must lie in 1..64, got %d" % cap)
+    d2 = torch.empty((B, H, W), dtype=torch.uint16, device=mask.device)
+    call("xv2_edt_sq", mask, B, H, W, cap, d2)
+    return d2
+
+
+def split_buildings(mask, r2, sweeps_per_call=8, return_labels=False):
+    """Cut a mask where buildings touch (include/xv2.h, "split touching buildings"): mask uint8 [B,H,W], r2 the squared
+    erosion radius in 1..4095.  Seeds, then xv2_split_grow with sweeps_per_call sweeps per call until a call's last sweep
+    changes nothing (one int32 is read back per call), then the cut.  Returns (out uint8 [B,H,W] with the mask's values kept,
+    the number of grow calls), and with return_labels also the int32 [B,H,W] map L of seed labels before the cut."""
+    mask, B, H, W = _split_mask("split_buildings", mask)
+    r2, sweeps = int(r2), int(sweeps_per_call)
+    if not 1 <= r2 <= 4095:
+        raise ValueError("split_buildings: r2 must lie in 1..4095, got %d" % r2)
+    if sweeps < 1:
+        raise ValueError("split_buildings: sweeps_per_call must be at least 1, got %d" % sweeps)
+    ws = _ws(int(query("xv2_split_workspace", B, H, W)), mask)
+    pending = torch.empty((1,), dtype=torch.int32, device=mask.device)
+    call("xv2_split_seed", mask, B, H, W, r2, ws)
+    calls = 0
+    while True:
+        call("xv2_split_grow", mask, B, H, W, sweeps, ws, pending)
+        calls += 1
+        if int(pending.item()) == 0:
+            break
+    out = torch.empty_like(mask)
+    labels = torch.empty((B, H, W), dtype=torch.int32, device=mask.device) if return_labels else None
+    call("xv2_split_finish", mask, B, H, W, ws, out, labels)
+    return (out, calls, labels) if return_labels else (out, calls)

@@ -9,7 +9,9 @@ checkpoint only its map is written: the localization map is then the 0.3 thresho
 decoded class of every pixel.  --buildings adds <stem>_buildings.csv (one row per predicted building: box, area, centroid,
 damage class, pixel counts, confidence) and <stem>_buildings.json (totals), computed on the GPU (xview2_amd.utils.buildings).
 --polygons adds <stem>_buildings.geojson: the outline of every building with its holes, traced on the GPU from the same label
-map (xview2_amd.utils.polygons), with the table's row as properties; it implies --buildings."""
+map (xview2_amd.utils.polygons), with the table's row as properties; it implies --buildings.  --split R cuts the localization
+map where buildings touch (xview2_amd.utils.split) before any of these outputs is made: the PNGs, the table and the outlines
+all come from the split maps."""
 import os
 from argparse import ArgumentDefaultsHelpFormatter, ArgumentParser
 
@@ -39,6 +41,8 @@ def get_parser():
     arg("--buildings", action="store_true", help="also write <stem>_buildings.csv / .json: one row per predicted building")
     arg("--polygons", action="store_true", help="also write <stem>_buildings.geojson: one outline per predicted building "
         "(implies --buildings)")
+    arg("--split", type=int, default=0, metavar="R", help="cut buildings that touch: erosion radius in pixels, 0 = off; applied "
+        "after --dilate (a dilation after it would close the cuts again) and before the vote of --components")
     return parser
 
 
@@ -121,7 +125,7 @@ def main(argv=None):
         dmg_map = (scene.decode_damage(dmg_maps, dmg.kind) if dmg is not None
                    else torch.ones((H, W), dtype=torch.int32, device=device))
         pre_png, post_png = post_process_tiles(loc_map, dmg_map, args.components and dmg is not None, args.dilate,
-                                               args.dilation_rate)
+                                               args.dilation_rate, split=args.split)
         if loc is not None:
             Image.fromarray(pre_png.cpu().numpy()).save(stem + "_localization_prediction.png")
         if dmg is not None:

@@ -10,10 +10,13 @@ JSON depends on the integers alone.
 
 What this does not do:
   * Labelled buildings that touch in the raster are ONE building here: the target PNG carries no instance ids.
+    --split_targets R cuts them apart by shape (utils/split.py) before they are labelled, --split R does the same to the
+    prediction; neither knows the labelled instances.
   * There is no minimum-area filter: a one-pixel component is a building on either side.
   * There is no georeferencing: boxes and ids are pixel coordinates and row numbers of the tile.
 
     python -m xview2_amd.utils.building_metrics PRED_DIR TARG_DIR OUT_JSON [--iou 1/2] [--per_building DIR] [--batch 16]
+                                                [--split R] [--split_targets R]
 """
 import json
 import os
@@ -203,11 +206,12 @@ class BuildingMetrics:
 
     get_path_handlers = XviewMetrics.get_path_handlers      # the same file naming, through the same PathHandler
 
-    def __init__(self, pred_dir, targ_dir, iou=(1, 2), batch=16):
+    def __init__(self, pred_dir, targ_dir, iou=(1, 2), batch=16, split=0, split_targets=0):
         self.pred_dir, self.targ_dir = Path(pred_dir), Path(targ_dir)
         assert self.pred_dir.is_dir(), "Could not find prediction directory: '%s'" % pred_dir
         assert self.targ_dir.is_dir(), "Could not find target directory: '%s'" % targ_dir
         self.iou, self.batch = (int(iou[0]), int(iou[1])), batch
+        self.split, self.split_targets = int(split), int(split_targets)
         self.get_path_handlers()
         self.get_matches()
         self.counts = [tile_counts(tm) for tm in self.matches]
@@ -229,6 +233,12 @@ class BuildingMetrics:
             for i in range(0, len(self.path_handlers), self.batch):
                 tiles = list(pool.map(_load, self.path_handlers[i:i + self.batch]))
                 lp, dp, lt, dt = (torch.from_numpy(np.stack([t[k] for t in tiles])).to(dev) for k in range(4))
+                if self.split or self.split_targets:
+                    from .split import split_maps
+                    if self.split:
+                        lp, dp = split_maps(lp, dp, self.split)
+                    if self.split_targets:
+                        lt, dt = split_maps(lt, dt, self.split_targets)
                 self.matches.extend(match_maps(lp, dp, lt, dt, self.iou))
 
     def score_dict(self):
@@ -245,10 +255,11 @@ class BuildingMetrics:
         return paths
 
     @classmethod
-    def compute_score(cls, pred_dir, targ_dir, out_fp, iou=(1, 2), per_building=None, batch=16):
+    def compute_score(cls, pred_dir, targ_dir, out_fp, iou=(1, 2), per_building=None, batch=16, split=0, split_targets=0):
         """write the object-level metrics JSON to out_fp (and the per-building CSVs into per_building, when given); batch:
-        tiles per call of the kernels"""
-        self = cls(pred_dir, targ_dir, iou, batch)
+        tiles per call of the kernels; split, split_targets: radius of utils.split on the predicted and on the labelled pair
+        before the buildings are labelled (0 = off)"""
+        self = cls(pred_dir, targ_dir, iou, batch, split, split_targets)
         d = self.score_dict()
         with open(out_fp, "w") as f:
             json.dump(d, f, indent=1, sort_keys=True)
@@ -277,10 +288,14 @@ def get_parser():
     p.add_argument("--iou", type=_iou_arg, default=(1, 2), help="IoU threshold of a match, N/D or a decimal, at least 1/2")
     p.add_argument("--per_building", default=None, metavar="DIR", help="write one CSV per tile with one line per building")
     p.add_argument("--batch", type=int, default=16, help="tiles per call of the kernels")
+    p.add_argument("--split", type=int, default=0, metavar="R", help="cut predicted buildings that touch before labelling them: "
+                   "erosion radius in pixels, 0 = off")
+    p.add_argument("--split_targets", type=int, default=0, metavar="R", help="the same for the labelled buildings, so that "
+                   "touching labelled buildings count separately")
     return p
 
 
 if __name__ == "__main__":
     a = get_parser().parse_args()
     compute_score(os.path.expanduser(a.pred_dir), os.path.expanduser(a.targ_dir), os.path.expanduser(a.out_fp), a.iou,
-                  os.path.expanduser(a.per_building) if a.per_building else None, a.batch)
+                  os.path.expanduser(a.per_building) if a.per_building else None, a.batch, a.split, a.split_targets)

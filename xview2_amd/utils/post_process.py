@@ -18,12 +18,16 @@ Semantics are the reference's (post_process.py:27-47), bit for bit, with these d
      output: 0..255 without --components, 1..4 with it (the vote keeps four classes per building); otherwise
      ValueError, where the reference would vote over it and write a PNG its scorer rejects.
 
-    python -m xview2_amd.utils.post_process --results R [--components] [--dilate [--dilation_rate 3]] [--buildings] [--polygons]
+    python -m xview2_amd.utils.post_process --results R [--components] [--dilate [--dilation_rate 3]] [--split R]
+                                            [--buildings] [--polygons]
 
 --buildings also writes buildings/test_buildings_NNNNN.csv per pair: one row per predicted building of the two PNGs
 (xview2_amd.utils.buildings), its confidence from the localization probabilities.  --polygons (which implies --buildings)
 adds buildings/test_buildings_NNNNN.geojson: the outline of every building, traced from the same label map
-(xview2_amd.utils.polygons).
+(xview2_amd.utils.polygons).  --split R cuts the localization map where buildings touch (xview2_amd.utils.split: erosion
+by a disc of radius R, cores grown back, a 1-pixel cut where they meet) and masks the damage map with it.  The order is fuse,
+dilate, split, vote: a dilation after the split would close the cuts again, and the vote of --components is then taken per
+split piece.  The PNGs, the CSV and the GeoJSON all come from the split maps.
 """
 import os
 from argparse import ArgumentDefaultsHelpFormatter, ArgumentParser, ArgumentTypeError
@@ -45,14 +49,23 @@ def _check_rate(dilate, dilation_rate):
     return r
 
 
-def post_process_tiles(loc, dmg, components=False, dilate=False, dilation_rate=3, workspace=None):
+def post_process_tiles(loc, dmg, components=False, dilate=False, dilation_rate=3, workspace=None, split=0):
     """uint8 (pre, post) on the device.  loc: fp32 [H,W] or [B,H,W]; dmg: [4|5,H,W] / [B,4|5,H,W] probabilities or an
-    [H,W] / [B,H,W] label map.  Unbatched input gives unbatched output."""
+    [H,W] / [B,H,W] label map.  Unbatched input gives unbatched output.  split > 0: fuse and dilate first, cut pre where
+    buildings touch (utils.split.split_maps with that radius) and mask post with it, and only then, with components, vote
+    per split piece: a second pass over the split maps (pre' as the localization, post' as a label map, no dilation)."""
     rate = _check_rate(dilate, dilation_rate)
     single = loc.dim() == 2
     if single:
         loc, dmg = loc.unsqueeze(0), dmg.unsqueeze(0)
-    pre, post = ops.postprocess(loc, dmg, components=components, rate=rate, workspace=workspace)
+    if split:
+        from .split import split_maps
+        pre, post = ops.postprocess(loc, dmg, components=False, rate=rate, workspace=workspace)
+        pre, post = split_maps(pre, post, split)
+        if components:
+            pre, post = ops.postprocess(pre.float(), post.to(torch.int32), components=True, rate=0, workspace=workspace)
+    else:
+        pre, post = ops.postprocess(loc, dmg, components=components, rate=rate, workspace=workspace)
     return (pre[0], post[0]) if single else (pre, post)
 
 
@@ -94,7 +107,8 @@ def post_process(args, pre_path, post_path):
     results = getattr(args, "results", "/results")
     dev = _device()
     loc, dmg = _to_device(np.load(pre_path), dev), _to_device(np.load(post_path), dev)
-    pre, post = post_process_tiles(loc, dmg, args.components, args.dilate, args.dilation_rate)
+    pre, post = post_process_tiles(loc, dmg, args.components, args.dilate, args.dilation_rate,
+                                   split=getattr(args, "split", 0))
     _save(pre.cpu().numpy(), os.path.join(results, "predictions", _out_name(pre_path)))
     _save(post.cpu().numpy(), os.path.join(results, "predictions", _out_name(post_path)))
 
@@ -103,6 +117,10 @@ def run(args):
     """the CLI: every probs/*localization* with its probs/*damage* partner (sorted pairing, as the reference), --batch
     pairs per GPU call, PNGs written from a small thread pool"""
     rate = _check_rate(args.dilate, args.dilation_rate)
+    split = getattr(args, "split", 0)
+    if split:
+        from .split import check_radius
+        split = check_radius(split)
     if args.batch < 1:
         raise ValueError("--batch must be >= 1, got %d" % args.batch)
     pred_dir = os.path.join(args.results, "predictions")
@@ -128,8 +146,8 @@ def run(args):
                 key = (len(ks),) + tuple(lshape)
                 if key not in workspace and (args.components or rate):
                     workspace[key] = ops.postprocess_workspace(len(ks), lshape[0], lshape[1], args.components, dev)
-                pre, post = ops.postprocess(loc, dmg, components=args.components, rate=rate,
-                                            workspace=workspace.get(key))
+                pre, post = post_process_tiles(loc, dmg, args.components, args.dilate, args.dilation_rate,
+                                               workspace.get(key), split=split)
                 want_polygons = getattr(args, "polygons", False)
                 if getattr(args, "buildings", False) or want_polygons:
                     from . import buildings
@@ -172,6 +190,8 @@ def get_parser():
     arg("--buildings", action="store_true", help="Also write buildings/<name>.csv per pair: one row per predicted building")
     arg("--polygons", action="store_true", help="Also write buildings/<name>.geojson per pair: one outline per predicted "
         "building (implies --buildings)")
+    arg("--split", type=int, default=0, metavar="R", help="Cut buildings that touch: erosion radius in pixels, 0 = off.  "
+        "Applied after --dilate (a dilation after it would close the cuts again) and before the vote of --components")
     return parser
 
 
