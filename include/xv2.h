@@ -967,6 +967,48 @@ int xv2_polygon_count(const int32_t* labels, int B, int H, int W, void* workspac
 int xv2_polygon_trace(const int32_t* labels, int B, int H, int W, int64_t total_edges, int64_t total_vertices,
                       void* workspace, int64_t* rings, int32_t* verts, int32_t* ring_count, int32_t* status, void* stream);
 
+/* ---- tolerance simplification of the outlines (simplify.hip, xview2_amd/utils/polygons.py --simplify T) ---------------------
+ * Douglas-Peucker on every ring of a ring table, exterior or hole, each on its own, in integers: the result is unique and
+ * compared with ==.
+ * Tolerance.  T is in pixels and is quantised once on the host to q = round(16 T), 0 <= q <= 65535.  The rule is stated in q.
+ * Extent.  Only differences of coordinates enter.  A ring whose extent (max - min) exceeds 32767 in x or in y is copied
+ * unchanged with flag 2 (this is looked at first, whatever n is).  Within that limit every quantity below fits an unsigned 64-bit word: every product is < 2^62 and
+ * q^2 L2 < 2^63.
+ * Anchors.  A ring's vertices are v[0..n-1], and v[n] means v[0].  Anchor 0 is the ring's first vertex (the trace starts every
+ * ring at its leader edge, so this is canonical).  Anchor m is the vertex with the largest squared distance from v[0], the
+ * lowest index winning ties.  If that distance is 0, or n < 3, the ring is copied unchanged with flag 1.  Otherwise the ring
+ * is the two open chains [0..m] and [m..n].
+ * Key of an interior vertex P of a chain segment with ends A, B.  With d = B - A, L2 = d.d, v = P - A and t = v.d:
+ *   L2 == 0 (a hole ring can pass one corner twice):  key = v.v,                     scale = 1
+ *   t <= 0:                                           key = (v.v) L2,                scale = L2
+ *   t >= L2:                                          key = ((P - B).(P - B)) L2,    scale = L2
+ *   otherwise:                                        key = (v.x d.y - v.y d.x)^2,   scale = L2
+ * That is the squared distance to the segment, not to the line, times scale.
+ * Split.  A segment's farthest vertex is the one with the largest key, the lowest index winning ties.  It is kept, and the
+ * segment splits there, iff key > (q^2 scale) >> 8, which is exactly dist > T because key is an integer.  Otherwise every
+ * interior vertex of the segment is dropped.  A segment's decision depends on the segment alone, so the order in which
+ * segments are looked at (recursive, or all open segments of a ring at once) does not enter the result.
+ * Collapse.  If fewer than 3 vertices of a ring survive, the ring is copied unchanged with flag 1: no building and no hole
+ * is ever lost, and the ring count never changes.
+ * Order.  The kept vertices stay in ring order and start at v[0].
+ * Not promised.  Rings are simplified independently: the outlines of neighbouring buildings may cross afterwards, so may a
+ * hole and its exterior, and a simplified ring may intersect itself.  The sign of 2A is recomputed, not guaranteed.
+ * Inputs.  rings int64 [n_rings][8] and verts int32 [total_vertices][2] as xv2_polygon_trace writes them; columns 2 (vertices)
+ * and 3 (offset) are read; the offsets must be contiguous in row order and start at 0 (column 3 of row r is the sum of column
+ * 2 over the rows before it, and the columns 2 sum to total_vertices).  A row whose vertex range does not lie inside the
+ * vertex array is not simplified, gets 0 vertices and writes none.
+ * Outputs.  out_rings int64 [n_rings][8]: the same rows with column 2 = kept vertices, 3 = new offset, 4 = 2A of the kept
+ * vertices (64-bit wrap-around arithmetic: exact whenever it fits), 7 = the flag: 0 simplified or left unchanged by the rule,
+ * 1 would collapse and was copied, 2 extent over 32767 and was copied.  out_verts int32 [total_vertices][2], compacted in the
+ * same ring order: only its first out_total rows are written.  out_total: device int64, the sum of column 2.
+ * Three launches; nothing is read back between them; no float operation; the atomics are integer max, min and add, so the
+ * same bits come out of every run and on every stream.  0 <= n_rings, total_vertices < 2^31; the workspace query (44 bytes
+ * per vertex and 24 per ring) is 0 outside that; the workspace needs no clearing.  verts, out_verts and the workspace must be
+ * 8-byte aligned; outputs must not overlap inputs.  A bad argument is XV2_EINVAL before anything is enqueued. */
+size_t xv2_polygon_simplify_workspace(int64_t n_rings, int64_t total_vertices);
+int xv2_polygon_simplify(const int64_t* rings, const int32_t* verts, int64_t n_rings, int64_t total_vertices, int q,
+                         void* workspace, int64_t* out_rings, int32_t* out_verts, int64_t* out_total, void* stream);
+
 /* ---- polygons -> masks (rasterize.hip, xview2_amd/utils/rasterize.py): the inverse of the outlines above ----------------------
  * Coordinates.  Vertices are int32 in units of 2^-k pixel, k = frac_bits in 0..8.  Pixel (y,x) is sampled at the point
  * s = ((x << k) + off, (y << k) + off).  off = 0 samples the lattice point (a vertex is a pixel index, the convention of the

@@ -2644,6 +2644,45 @@ def polygon_trace(labels, total_edges, total_vertices):
     return rings, verts, ring_count
 
 
+def polygon_simplify(rings, verts, n_rings, q, checked=False):
+    """Douglas-Peucker on every ring of a ring table (include/xv2.h xv2_polygon_simplify).  rings int64 [>= n_rings, 8] and
+    verts int32 [V, 2] as polygon_trace returns them, n_rings the rows in use (ring_count.sum()), q = round(16 T) in
+    0..65535.  Returns (out_rings int64 [n_rings, 8], out_verts int32 [V, 2], out_total int64 [1]) on the device; only the
+    first out_total rows of out_verts are written.  The offsets in column 3 must be contiguous and start at 0, and the
+    columns 2 must sum to V: that is checked here on the device (one flag is read back) unless the caller vouches for a
+    table that comes straight from polygon_trace with checked=True."""
+    _need_cuda(rings)
+    _need_cuda(verts)
+    if rings.dtype != torch.int64 or rings.dim() != 2 or rings.shape[1] != POLYGON_RING_COLS:
+        raise ValueError("polygon_simplify: rings must be int64 [R, 8], got %s %s" % (rings.dtype, tuple(rings.shape)))
+    if verts.dtype != torch.int32 or verts.dim() != 2 or verts.shape[1] != 2:
+        raise ValueError("polygon_simplify: verts must be int32 [V, 2], got %s %s" % (verts.dtype, tuple(verts.shape)))
+    if verts.device != rings.device:
+        raise ValueError("polygon_simplify: rings are on %s but verts on %s" % (rings.device, verts.device))
+    R, V, q = int(n_rings), int(verts.shape[0]), int(q)
+    if not 0 <= R <= rings.shape[0]:
+        raise ValueError("polygon_simplify: n_rings=%d outside 0 .. %d, the rows of rings" % (R, rings.shape[0]))
+    if not 0 <= q <= 65535:
+        raise ValueError("polygon_simplify: q must lie in 0..65535, got %d" % q)
+    need = int(query("xv2_polygon_simplify_workspace", R, V))
+    if need == 0:
+        raise ValueError("polygon_simplify: %d rings and %d vertices outside the supported sizes (< 2^31)" % (R, V))
+    rings, verts = rings[:R].contiguous(), verts.contiguous()
+    if not checked:
+        n = rings[:, 2]
+        ends = torch.cumsum(n, 0)
+        if not bool(((n >= 0) & (rings[:, 3] == ends - n)).all()) or (int(ends[-1]) if R else 0) != V:
+            raise ValueError("polygon_simplify: the offsets (column 3) are not contiguous from 0, or the vertex counts "
+                             "(column 2) do not sum to the %d rows of verts" % V)
+    ws = _ws(need, rings)
+    out_rings = torch.empty((R, POLYGON_RING_COLS), dtype=torch.int64, device=rings.device)
+    out_verts = torch.empty((V, 2), dtype=torch.int32, device=rings.device)
+    out_total = torch.empty((1,), dtype=torch.int64, device=rings.device)
+    call("xv2_polygon_simplify", rings if R else None, verts if V else None, R, V, q, ws, out_rings if R else None,
+         out_verts if V else None, out_total)
+    return out_rings, out_verts, out_total
+
+
 def rasterize_polygons(tables, n_edges, n_features, n_work, frac_bits, off, B, H, W, device=None):
     """Polygons -> a painted uint8 [B,H,W] map on the device (include/xv2.h xv2_rasterize_polygons).  tables: the int32 numpy
     buffer of utils.rasterize.pack (edges, features, work items); it is uploaded once here and its host copy is what the

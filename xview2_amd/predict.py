@@ -9,7 +9,8 @@ checkpoint only its map is written: the localization map is then the 0.3 thresho
 decoded class of every pixel.  --buildings adds <stem>_buildings.csv (one row per predicted building: box, area, centroid,
 damage class, pixel counts, confidence) and <stem>_buildings.json (totals), computed on the GPU (xview2_amd.utils.buildings).
 --polygons adds <stem>_buildings.geojson: the outline of every building with its holes, traced on the GPU from the same label
-map (xview2_amd.utils.polygons), with the table's row as properties; it implies --buildings.  --split R cuts the localization
+map (xview2_amd.utils.polygons), with the table's row as properties; it implies --buildings.  --simplify T
+reduces those outlines by Douglas-Peucker with a tolerance of T pixels, on the GPU; it changes the GeoJSON only.  --split R cuts the localization
 map where buildings touch (xview2_amd.utils.split) before any of these outputs is made: the PNGs, the table and the outlines
 all come from the split maps."""
 import os
@@ -41,6 +42,8 @@ def get_parser():
     arg("--buildings", action="store_true", help="also write <stem>_buildings.csv / .json: one row per predicted building")
     arg("--polygons", action="store_true", help="also write <stem>_buildings.geojson: one outline per predicted building "
         "(implies --buildings)")
+    arg("--simplify", type=float, default=0.0, metavar="T", help="with --polygons: drop outline vertices that lie within T "
+        "pixels of what is left (Douglas-Peucker per ring, 0 <= T < 4096); 0 = off.  No value is recommended")
     arg("--split", type=int, default=0, metavar="R", help="cut buildings that touch: erosion radius in pixels, 0 = off; applied "
         "after --dilate (a dilation after it would close the cuts again) and before the vote of --components")
     return parser
@@ -91,6 +94,9 @@ def main(argv=None):
     from . import ops, scene
     from .utils.post_process import post_process_tiles
     scene.check_window(args.window, args.overlap)
+    if args.simplify:
+        from .utils.polygons import quantise_tolerance
+        quantise_tolerance(args.simplify)
     pairs = pair_inputs(args.pre, args.post if args.ckpt_dmg is not None else None)
     if not torch.cuda.is_available():
         raise RuntimeError("xview2_amd.predict runs on the MI355X only; there is no CPU fallback")
@@ -140,7 +146,8 @@ def main(argv=None):
             buildings.write_summary(stem + "_buildings.json", records)
             if args.polygons:
                 from .utils import polygons
-                polygons.write_geojson(stem + "_buildings.geojson", polygons.building_polygons(pre_png, labels), records)
+                polygons.write_geojson(stem + "_buildings.geojson", polygons.building_polygons(pre_png, labels, args.simplify),
+                                       records)
         if args.save_probs:
             if loc is not None:
                 np.save(stem + "_localization_probs.npy", loc_maps.cpu().numpy())

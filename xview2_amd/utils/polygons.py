@@ -3,15 +3,25 @@
 The rings are traced on the MI355X (csrc/polygons.hip, xv2_polygon_count and xv2_polygon_trace) from the label map of the
 localization PNG: the boundary of every 4-connected component of pre != 0, ordered into closed rings of lattice corners
 (include/xv2.h states the contract).  Pixel (y, x) covers [x, x + 1] x [y, y + 1], so coordinates run 0..W and 0..H, y down.
-Collinear points are dropped and nothing else is simplified.  Read as plain (x, y) pairs the exterior rings have positive
-and the holes negative signed area.  Every value is an integer, so the files have the same bytes on every run.
+Collinear points are dropped and, unless a tolerance is given, nothing else is simplified.  Read as plain (x, y) pairs the
+exterior rings have positive and the holes negative signed area.  Every value is an integer, so the files have the same bytes
+on every run.
+
+With a tolerance T > 0 in pixels (`simplify=T`, `--simplify T`) every ring, exterior or hole, is then reduced on the MI355X by
+Douglas-Peucker in exact integers (csrc/simplify.hip, xv2_polygon_simplify; include/xv2.h states the rule): a vertex survives
+iff it lies more than T from the chord of its chain, T quantised to sixteenths of a pixel.  Every dropped vertex lies within
+T of the ring that is left, every coordinate stays an integer corner, and no ring is lost (a ring that would collapse below
+three vertices is kept as traced).  Rings are simplified one by one: neighbouring outlines, or a hole and its exterior, may
+cross afterwards, a ring may cut itself, and the table's area stays the pixel area.  No tolerance is recommended: there is
+no xBD imagery at hand to score one.
 
 One known property: a hole ring may touch itself at a corner (two hole pixels that meet diagonally are one ring that
 passes the shared corner twice).  That is topologically right, but strict OGC validators call such a ring non-simple.
 
-    python -m xview2_amd.utils.polygons PRE.png POST.png OUT.geojson
+    python -m xview2_amd.utils.polygons PRE.png POST.png OUT.geojson [--simplify T]
 """
 import json
+import math
 import os
 
 import numpy as np
@@ -41,12 +51,25 @@ def group_rings(rings, verts):
     return polys
 
 
-def building_polygons(pre, labels=None):
+def quantise_tolerance(T):
+    """the tolerance in pixels -> q = round(16 T) (halves up), the integer the rule of include/xv2.h is stated in; 0 <= T <
+    4096, and the few T just below 4096 that would round to 65536 give 65535"""
+    T = float(T)
+    if not 0.0 <= T < 4096.0:                # (NaN fails both comparisons)
+        raise ValueError("the simplification tolerance must satisfy 0 <= T < 4096 pixels, got %r" % T)
+    return min(int(math.floor(16.0 * T + 0.5)), 65535)
+
+
+def building_polygons(pre, labels=None, simplify=0.0):
     """pre: uint8 [H,W] or [B,H,W] device map (the label map of the localization PNG).  Returns per tile (a list of lists;
     one list for unbatched input) the polygons of its buildings in the building table's row order.  labels: the int32
-    labels of pre != 0 when the caller has them already (utils.buildings.building_table(..., return_labels=True))."""
+    labels of pre != 0 when the caller has them already (utils.buildings.building_table(..., return_labels=True)).
+    simplify: the tolerance T in pixels; with quantise_tolerance(T) == 0 nothing new is launched, otherwise the traced rings
+    are simplified on the device, only the simplified table and its vertices are read back, and every polygon carries
+    "simplified": q."""
     import torch
     from .. import ops
+    q = quantise_tolerance(simplify)
     single = pre.dim() == 2
     if single:
         pre = pre.unsqueeze(0)
@@ -60,9 +83,16 @@ def building_polygons(pre, labels=None):
     counts = ops.polygon_count(labels).cpu().numpy()      # the only read-back before the last launch: it sizes the rest
     rings, verts, ring_count = ops.polygon_trace(labels, int(counts[:, 0].sum()), int(counts[:, 1].sum()))
     n = ring_count.cpu().numpy().astype(np.int64)
+    if q:
+        rings, verts, total = ops.polygon_simplify(rings, verts, int(n.sum()), q, checked=True)
+        verts = verts[:int(total.item())]
     rings, verts = rings[:int(n.sum())].cpu().numpy(), verts.cpu().numpy().tolist()
     ends = np.cumsum(n)
     out = [group_rings(rings[e - k:e], verts) for k, e in zip(n.tolist(), ends.tolist())]
+    if q:
+        for tile in out:
+            for p in tile:
+                p["simplified"] = q
     return out[0] if single else out
 
 
@@ -78,14 +108,17 @@ def to_wkt(polygon):
 
 def _match(polygons, records):
     """records (utils.buildings.to_records rows, or None) in the polygons' order: equally many, and every record's box is
-    its polygon's extent"""
+    its polygon's extent.  A polygon that carries "simplified": q may have lost the vertices that touched the box: its
+    extent must lie inside the box and fall short of it by at most ceil(q / 16) pixels on each side."""
     if records is None:
         return [None] * len(polygons)
     if len(records) != len(polygons):
         raise ValueError("%d polygons but %d building records" % (len(polygons), len(records)))
     for i, (p, r) in enumerate(zip(polygons, records)):
         xs, ys = [v[0] for v in p["exterior"]], [v[1] for v in p["exterior"]]
-        if (min(ys), min(xs), max(ys), max(xs)) != (r["y0"], r["x0"], r["y1"] + 1, r["x1"] + 1):
+        ext, box = (min(ys), min(xs), max(ys), max(xs)), (r["y0"], r["x0"], r["y1"] + 1, r["x1"] + 1)
+        slack = (int(p["simplified"]) + 15) // 16 if "simplified" in p else 0
+        if not all(0 <= s * (e - b) <= slack for e, b, s in zip(ext, box, (1, 1, -1, -1))):
             raise ValueError("record %d (id %s) is not the building of polygon %d (root %d): the records must be in the "
                              "polygons' order" % (i, r.get("id"), i, p["root"]))
     return records
@@ -122,11 +155,26 @@ def write_xbd_json(path, polygons, records):
         f.write('{"features": {"xy": [\n' + ",\n".join(lines) + ("\n" if lines else "") + "]}}\n")
 
 
+def get_parser():
+    from argparse import ArgumentParser
+    usage = "python -m xview2_amd.utils.polygons PRE.png POST.png OUT.geojson [--simplify T]"
+
+    class Parser(ArgumentParser):
+        def error(self, message):            # the usage line is the exit message, as before there were options
+            raise SystemExit("usage: %s\n%s" % (usage, message))
+    parser = Parser(prog="python -m xview2_amd.utils.polygons", usage=usage)
+    parser.add_argument("pre", metavar="PRE.png")
+    parser.add_argument("post", metavar="POST.png")
+    parser.add_argument("out", metavar="OUT.geojson")
+    parser.add_argument("--simplify", type=float, default=0.0, metavar="T", help="drop outline vertices that lie within T "
+                        "pixels of what is left (Douglas-Peucker per ring, 0 <= T < 4096); 0 = off")
+    return parser
+
+
 def main(argv=None):
-    import sys
-    argv = sys.argv[1:] if argv is None else argv
-    if len(argv) != 3:
-        raise SystemExit("usage: python -m xview2_amd.utils.polygons PRE.png POST.png OUT.geojson")
+    args = get_parser().parse_args(argv)
+    quantise_tolerance(args.simplify)
+    argv = [args.pre, args.post, args.out]
     import torch
     from PIL import Image
     from . import buildings
@@ -139,7 +187,7 @@ def main(argv=None):
     pre_d = torch.from_numpy(pre.copy()).to(dev)
     rows, labels = buildings.building_table(pre_d, torch.from_numpy(post.copy()).to(dev), return_labels=True)
     records = buildings.to_records(rows, pre.shape[0], pre.shape[1], confidence=False)
-    write_geojson(argv[2], building_polygons(pre_d, labels), records)
+    write_geojson(argv[2], building_polygons(pre_d, labels, args.simplify), records)
     return len(records)
 
 

@@ -19,12 +19,13 @@ Semantics are the reference's (post_process.py:27-47), bit for bit, with these d
      ValueError, where the reference would vote over it and write a PNG its scorer rejects.
 
     python -m xview2_amd.utils.post_process --results R [--components] [--dilate [--dilation_rate 3]] [--split R]
-                                            [--buildings] [--polygons]
+                                            [--buildings] [--polygons [--simplify T]]
 
 --buildings also writes buildings/test_buildings_NNNNN.csv per pair: one row per predicted building of the two PNGs
 (xview2_amd.utils.buildings), its confidence from the localization probabilities.  --polygons (which implies --buildings)
 adds buildings/test_buildings_NNNNN.geojson: the outline of every building, traced from the same label map
-(xview2_amd.utils.polygons).  --split R cuts the localization map where buildings touch (xview2_amd.utils.split: erosion
+(xview2_amd.utils.polygons); --simplify T reduces those outlines by Douglas-Peucker with a tolerance of T pixels and changes the
+GeoJSON only.  --split R cuts the localization map where buildings touch (xview2_amd.utils.split: erosion
 by a disc of radius R, cores grown back, a 1-pixel cut where they meet) and masks the damage map with it.  The order is fuse,
 dilate, split, vote: a dilation after the split would close the cuts again, and the vote of --components is then taken per
 split piece.  The PNGs, the CSV and the GeoJSON all come from the split maps.
@@ -123,6 +124,10 @@ def run(args):
         split = check_radius(split)
     if args.batch < 1:
         raise ValueError("--batch must be >= 1, got %d" % args.batch)
+    simplify = getattr(args, "simplify", 0.0)
+    if simplify:
+        from .polygons import quantise_tolerance
+        quantise_tolerance(simplify)
     pred_dir = os.path.join(args.results, "predictions")
     os.makedirs(pred_dir, exist_ok=True)
     pre_paths = sorted(glob(os.path.join(args.results, "probs", "*localization*")))
@@ -155,7 +160,7 @@ def run(args):
                     tables, labels = buildings.building_table(pre, post, loc, return_labels=True)
                     if want_polygons:
                         from . import polygons
-                        outlines = polygons.building_polygons(pre, labels)
+                        outlines = polygons.building_polygons(pre, labels, simplify)
                     for j, rows in enumerate(tables):
                         recs = buildings.to_records(rows, lshape[0], lshape[1])
                         name = os.path.join(args.results, "buildings", _buildings_name(pairs[ks[j]][0]))
@@ -190,6 +195,8 @@ def get_parser():
     arg("--buildings", action="store_true", help="Also write buildings/<name>.csv per pair: one row per predicted building")
     arg("--polygons", action="store_true", help="Also write buildings/<name>.geojson per pair: one outline per predicted "
         "building (implies --buildings)")
+    arg("--simplify", type=float, default=0.0, metavar="T", help="With --polygons: drop outline vertices that lie within T "
+        "pixels of what is left (Douglas-Peucker per ring, 0 <= T < 4096); 0 = off.  No value is recommended")
     arg("--split", type=int, default=0, metavar="R", help="Cut buildings that touch: erosion radius in pixels, 0 = off.  "
         "Applied after --dilate (a dilation after it would close the cuts again) and before the vote of --components")
     return parser
