@@ -734,6 +734,21 @@ int xv2_optim_guard_ctx(const void* guard);
 int xv2_ema_update_dev(float* ema, const float* param, int64_t n, double decay, int warmup, int* count_dev,
                        const void* guard, void* stream);
 
+/* Gradient accumulation over micro-batches (--accumulate_grad_batches): the HIP backward kernels overwrite their slice of the
+ * flat gradient buffer, so the sum over a group of micro-batches is kept in a second flat buffer `acc` of the same layout.  One
+ * launch over acc[0 .. n) and grad[0 .. n), any slice of the two buffers (the pointers need not be their bases):
+ *   mode 0  open    acc[i]  = grad[i]                     8 bytes per element    after the group's first micro-batch
+ *   mode 1  add     acc[i]  = acc[i] + grad[i]           12 bytes per element    after every further one but the last
+ *   mode 2  close   grad[i] = acc[i] + grad[i]           12 bytes per element    after the last: `acc` is only read
+ * Each element gets exactly one IEEE fp32 addition, round to nearest even: no fma, no scaling, no reordering.  The gradient of a
+ * group of m micro-batches g1 .. gm is therefore ((g1 + g2) + g3 ... ) + gm bit for bit, summed in micro-batch order, a function
+ * of the inputs alone - what torch's own .grad accumulation computes.  A non-finite element reaches only its own element.  The
+ * division by m is NOT done here: it rides in the rule's grad_scale, as the reducer's 1 / world does.  16-byte loads and stores
+ * when both pointers are 16-byte aligned, the same operation in a scalar loop for the tail and otherwise.
+ * n == 0: OK without a launch.  n < 0, n > 0 with a NULL pointer, a mode outside 0 .. 2, or acc[0 .. n) and grad[0 .. n)
+ * overlapping: XV2_EINVAL before any launch. */
+int xv2_grad_accumulate(float* acc, float* grad, int64_t n, int mode, void* stream);
+
 /* ---- in-library kernel timing (bench.py roofline leg) --------------------------------------
  * When enabled, every launch of an MFMA kernel (implicit-GEMM conv / weight-gradient) is bracketed
  * by hipEvents on its own stream and tagged with its algorithmic FLOP count (2*M*N*K of the

@@ -72,6 +72,9 @@ _LAUNCH_FLAGS = [
     # an exponential moving average of the weights for validation, best.ckpt and evaluation (not flags of the reference's main.py)
     ("ema_decay", dict(type=float, default=0.0, help="decay of the weight average that validation and best.ckpt use (0: off)")),
     ("eval_ema", dict(action="store_true", help="--exec_mode eval: load the checkpoint's averaged weights (ema_state_dict)")),
+    # PL Trainer(accumulate_grad_batches): one optimizer step per K consecutive batches (not a flag of the reference's main.py)
+    ("accumulate_grad_batches", dict(type=int, default=1,
+                                     help="batches whose mean gradient takes one optimizer step (1: off)")),
     # synthetic-data knobs (not in the reference)
     ("train_size", dict(type=int, default=512)),
     ("eval_size", dict(type=int, default=1024)),
@@ -115,7 +118,8 @@ def main(argv=None):
                       sync_batchnorm=args.gpus > 1, accelerator="ddp" if args.gpus > 1 else None,
                       default_root_dir=args.results, checkpoint_callback=args.exec_mode == "train",
                       resume_from_checkpoint=checkpoint, gradient_clip_val=args.gradient_clip_val,
-                      skip_nonfinite=args.skip_nonfinite, ema_decay=args.ema_decay)
+                      skip_nonfinite=args.skip_nonfinite, ema_decay=args.ema_decay,
+                      accumulate_grad_batches=args.accumulate_grad_batches)
     if args.data == "synthetic":
         dm = SyntheticDataModule(args, device=trainer.device, rank=trainer.rank, train_size=args.train_size,
                                  eval_size=args.eval_size, steps_per_epoch=args.steps_per_epoch)

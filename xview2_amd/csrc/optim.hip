@@ -18,6 +18,9 @@
 //
 // EMA of the weights (xv2_ema_update_dev): a kernel of its own behind the rule, never fused into one - one streaming launch over
 // the average and the parameter buffer plus the counter increment, with the guard record passed explicitly.
+//
+// Gradient accumulation (xv2_grad_accumulate): one streaming launch over a second flat buffer and the gradient buffer, one
+// rounded addition per element in micro-batch order; no rule, guard or backward kernel knows about it.
 #include "xv2_common.h"
 #include "optim_ctx.h"
 #include <algorithm>
@@ -481,9 +484,60 @@ __global__ void __launch_bounds__(256) ema_update_kernel(float* __restrict__ ema
         ema[i] = ema_one(ema[i], param[i], om);
 }
 
+// ---- gradient accumulation over micro-batches -------------------------------------------------------------------
+// One rounded fp32 addition per element, acc[i] + grad[i] in that operand order (there is no product, so nothing contracts):
+// open copies grad into acc, add stores the sum into acc, close stores it into grad and only reads acc.  ema_update_kernel's
+// loop: 16-byte loads and stores when both pointers are 16-byte aligned, the same operation per element for the tail and
+// otherwise.
+enum AccumMode { ACCUM_OPEN = 0, ACCUM_ADD = 1, ACCUM_CLOSE = 2 };
+
+template <int MODE>
+__global__ void __launch_bounds__(256) grad_accumulate_kernel(float* __restrict__ acc, float* __restrict__ grad, int64_t n) {
+    const int64_t n4 = ((reinterpret_cast<uintptr_t>(acc) | reinterpret_cast<uintptr_t>(grad)) & 15) ? 0 : n >> 2;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+        const float4 g = reinterpret_cast<const float4*>(grad)[i];
+        if (MODE == ACCUM_OPEN) {
+            reinterpret_cast<float4*>(acc)[i] = g;
+        } else {
+            float4 a = reinterpret_cast<const float4*>(acc)[i];
+            a.x = a.x + g.x;
+            a.y = a.y + g.y;
+            a.z = a.z + g.z;
+            a.w = a.w + g.w;
+            reinterpret_cast<float4*>(MODE == ACCUM_ADD ? acc : grad)[i] = a;
+        }
+    }
+    for (int64_t i = n4 * 4 + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        if (MODE == ACCUM_OPEN)
+            acc[i] = grad[i];
+        else
+            (MODE == ACCUM_ADD ? acc : grad)[i] = acc[i] + grad[i];
+    }
+}
+
 }  // namespace xv2
 
 using namespace xv2;
+
+extern "C" int xv2_grad_accumulate(float* acc, float* grad, int64_t n, int mode, void* stream) {
+    XV2_CHECK_ARG(n >= 0, "grad_accumulate: n = %lld, must not be negative", (long long)n);
+    XV2_CHECK_ARG(mode >= ACCUM_OPEN && mode <= ACCUM_CLOSE, "grad_accumulate: unknown mode %d (0 open, 1 add, 2 close)", mode);
+    if (n == 0) return XV2_OK;
+    XV2_CHECK_ARG(acc && grad, "grad_accumulate: null accumulator or gradient buffer");
+    const uintptr_t a = reinterpret_cast<uintptr_t>(acc), g = reinterpret_cast<uintptr_t>(grad), bytes = (uintptr_t)n * sizeof(float);
+    XV2_CHECK_ARG(a + bytes <= g || g + bytes <= a, "grad_accumulate: the accumulator and the gradient buffer overlap");
+    // ema_update_kernel's grid: one float4 per thread up to 4096 blocks, grid-stride beyond 2^22 elements
+    const int grid = (int)std::min<int64_t>(cdiv(cdiv(n, 4), 256), 4096);
+    hipStream_t s = (hipStream_t)stream;
+    if (mode == ACCUM_OPEN)
+        hipLaunchKernelGGL(grad_accumulate_kernel<ACCUM_OPEN>, dim3(grid), dim3(256), 0, s, acc, grad, n);
+    else if (mode == ACCUM_ADD)
+        hipLaunchKernelGGL(grad_accumulate_kernel<ACCUM_ADD>, dim3(grid), dim3(256), 0, s, acc, grad, n);
+    else
+        hipLaunchKernelGGL(grad_accumulate_kernel<ACCUM_CLOSE>, dim3(grid), dim3(256), 0, s, acc, grad, n);
+    XV2_CHECK_LAUNCH();
+    return XV2_OK;
+}
 
 extern "C" size_t xv2_grad_guard_workspace(int64_t n) { return n > 0 ? (size_t)guard_blocks(n) * sizeof(double) : 0; }
 

@@ -10,6 +10,12 @@ sync_batchnorm=gpus > 1), main.py:106-107).
   small share of the gradients) so each RCCL call is bandwidth- not latency-bound; there is no per-parameter collective.
 * SyncBatchNorm: xview2_amd.nn.SYNC_BN makes every BN all-reduce its (sum, sum-of-squares) in forward and
   (sum g, sum g*xhat) in backward - same statistics as torch.nn.SyncBatchNorm.
+* Gradient accumulation (FlatOptimizer.accumulate): micro-batches that do not end their group run under
+  ``prepare(sync=False)`` and reduce nothing.  On the group's last micro-batch a bucket first gets the sum of the earlier ones
+  added (xv2_grad_accumulate, mode close, on the side stream behind the bucket's waits) and then travels as usual: each rank
+  reduces the group's total once, with the volume and the overlap of an ordinary step.  SyncBatchNorm is untouched: every
+  micro-batch normalises with its own statistics, exchanged across the ranks, and the running statistics move once per
+  micro-batch (K times per optimizer step), as torch's do.
 """
 import os
 
@@ -56,6 +62,7 @@ class GradReducer:
         self.world = dist.get_world_size() if dist.is_initialized() else 1
         self.enabled = self.world > 1 or (ops.FORCE_COLLECTIVES and dist.is_initialized())
         self.overlap = overlap
+        self.sync = True        # prepare(sync=False): the coming backward pass fills the slots and reduces nothing
         self.on_gpu = optimizer.flat_g.is_cuda
         if sync_bn and self.enabled:
             xnn.SYNC_BN = True
@@ -91,6 +98,8 @@ class GradReducer:
                 view = self.opt.flat_g[o:o + p.numel()].view_as(p)
                 view.copy_(p.grad)
                 p.grad = view
+            if not self.sync:          # a micro-batch that does not end its group: the slot is filled, nothing travels
+                return
             b = self.bucket_of[i]
             self.remaining[b] -= 1
             if self.remaining[b] == 0 and self.overlap:
@@ -111,21 +120,31 @@ class GradReducer:
                 wgs = ops.wgrad_stream()
                 if wgs is not None:
                     self.side.wait_stream(wgs)
+                if self.opt.pending > 0:
+                    # the last micro-batch of an accumulation group: the sum of the earlier ones joins this bucket here, behind
+                    # the same waits, so that the group's total is what travels - once, with an ordinary step's volume and overlap
+                    from ._capi import call
+                    call("xv2_grad_accumulate", self.opt.flat_acc[s:e], sl, e - s, 2)
                 self.handles.append(dist.all_reduce(sl, async_op=True))
         else:
             self.handles.append(dist.all_reduce(sl, async_op=True))
 
-    def prepare(self):
-        """call before backward"""
+    def prepare(self, sync=True):
+        """call before backward.  sync=False: a micro-batch that does not end its accumulation group (FlatOptimizer.accumulate
+        follows instead of finish): the hooks still move foreign gradients into their slots, no collective is launched"""
+        self.sync = bool(sync)
         if self.enabled:
             self.remaining = [len(m) for _, _, m in self.buckets]
             self.handles = []
 
     def finish(self):
         """call after backward: launches whatever did not fire (unused parameters keep zero grads) and makes
-        the compute stream wait for the collectives.  Returns the grad_scale for the optimizer."""
+        the compute stream wait for the collectives.  Returns the grad_scale for the optimizer (1 / world: the optimizer
+        folds in the 1 / m of an accumulation group itself)."""
         if not self.enabled:
             return 1.0
+        if not self.sync:
+            raise RuntimeError("GradReducer.finish() after prepare(sync=False): this micro-batch was not to be reduced")
         for b, r in enumerate(self.remaining):
             if r != 0 or not self.overlap:
                 self._launch(b)
@@ -135,6 +154,8 @@ class GradReducer:
         if self.on_gpu:
             torch.cuda.current_stream().wait_stream(self.side)
         self.handles = []
+        if self.opt.pending > 0:
+            self.opt.buckets_closed = True       # every bucket went through _launch: step() must not add flat_acc again
         # one-shot SyncBatchNorm exchange: a timed-out exchange poisons its results with NaN (loud by itself); every ~4000
         # exchanges (tens of steps) the host also reads the flag and names the rank
         check_peer_exchange(every=4000)

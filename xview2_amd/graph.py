@@ -12,7 +12,9 @@ from . import nn as xnn
 
 class GraphedStep:
     def __init__(self, step_fn, optimizer, static_inputs, warmup=2):
-        """step_fn(*static_inputs) -> loss tensor; it must zero grads, run backward and the optimizer step."""
+        """step_fn(*static_inputs) -> loss tensor; it must zero grads, run backward and the optimizer step.
+        Not wired to gradient accumulation (FlatOptimizer.accumulate): a group's micro-batches take different launches (open,
+        add, close) and its size reaches the rule as a host scalar, so a captured step is one whole optimizer step."""
         self.opt = optimizer
         self.inputs = static_inputs
         optimizer.sync_lr()

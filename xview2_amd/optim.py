@@ -8,6 +8,10 @@ data-parallel reducer (xview2_amd.dist) all-reduces contiguous slices without pa
 
 ``FlatEMA`` keeps an exponential moving average of that parameter buffer (one more launch per step) that validation,
 ``best.ckpt`` and evaluation can be taken from.
+
+Gradient accumulation (``FlatOptimizer.accumulate``): the backward kernels overwrite their slot, so the sum over a group of
+micro-batches is kept in a third flat buffer by one streaming launch per micro-batch, in micro-batch order; ``step`` adds it
+into the gradient buffer and folds the group's 1 / m into the rule's gradient scale.
 """
 import contextlib
 
@@ -61,6 +65,39 @@ class FlatOptimizer:
         self.step_dev = torch.zeros(1, dtype=torch.int32, device=dev) if dev.type == "cuda" else None
         self._lr_on_dev = lr
         self.guard = None                  # the gradient guard's device record (set_guard)
+        # gradient accumulation (accumulate): the running sum of a group's micro-batch gradients, flat_g's layout, allocated by
+        # the first accumulate() and never saved; `pending` counts the micro-batches it holds; buckets_closed: the reducer has
+        # already added it into every bucket of flat_g (dist.GradReducer), so step() must not do it again
+        self.flat_acc, self.pending, self.buckets_closed = None, 0, False
+
+    # ------------------------------------------------------------------ gradient accumulation
+    def accumulate(self):
+        """after backward() of a micro-batch that does NOT end its group, in place of step(): the micro-batch's gradient goes
+        into flat_acc (include/xv2.h xv2_grad_accumulate: a copy for the group's first, one rounded addition per element
+        afterwards), so the sum runs in micro-batch order.  zero_grad() stays the per-micro-batch call; the step() after the
+        group's last backward() adds flat_acc into flat_g and divides by the group's size through the rule's gradient scale."""
+        if not self.capturable:
+            raise RuntimeError("gradient accumulation runs on the GPU only (HIP kernels; there is no CPU fallback)")
+        from ._capi import call
+        ops.join_wgrad_stream()
+        self._gather_foreign_grads()       # shared weights' second contributions and torch-side gradients are in flat_g first
+        if self.flat_acc is None:
+            self.flat_acc = torch.empty_like(self.flat_g)
+        call("xv2_grad_accumulate", self.flat_acc, self.flat_g, self.total, 0 if self.pending == 0 else 1)
+        self.pending += 1
+
+    def _close_group(self, grad_scale):
+        """step() with micro-batches pending: every element of flat_g gets flat_acc added exactly once (here, unless the
+        reducer did it bucket by bucket before its collectives); returns the scale with the group's 1 / m folded in, divided
+        on the host in double like the reducer's 1 / world"""
+        if self.pending == 0:
+            return grad_scale
+        if not self.buckets_closed:
+            from ._capi import call
+            call("xv2_grad_accumulate", self.flat_acc, self.flat_g, self.total, 2)
+        scale = float(grad_scale / (self.pending + 1))
+        self.pending, self.buckets_closed = 0, False
+        return scale
 
     # ------------------------------------------------------------------ gradient guard
     def set_guard(self, max_norm=0.0, skip_nonfinite=False):
@@ -124,9 +161,11 @@ class FlatOptimizer:
             self._lr_on_dev = lr
 
     def step(self, grad_scale=1.0):
-        """one update; grad_scale multiplies the gradient first (the reducer's 1/world)"""
+        """one update; grad_scale multiplies the gradient first (the reducer's 1/world).  With micro-batches pending
+        (accumulate) it first closes their group: the guard and the rule see the group's sum once, scaled by 1 / m"""
         ops.join_wgrad_stream()      # weight-gradient kernels run on a side stream (ops.ASYNC_WGRAD)
         self._gather_foreign_grads()
+        grad_scale = self._close_group(grad_scale)
         self.step_count += 1
         if not self.capturable:
             raise RuntimeError("%s steps on the GPU only (HIP kernels; there is no CPU fallback)" % type(self).__name__)
@@ -179,6 +218,7 @@ class FlatAdamW(FlatOptimizer):
     def step(self, grad_scale=1.0):
         ops.join_wgrad_stream()      # weight-gradient kernels run on a side stream (ops.ASYNC_WGRAD)
         self._gather_foreign_grads()
+        grad_scale = self._close_group(grad_scale)
         self.step_count += 1
         lr = self.param_groups[0]["lr"]
         if self.capturable:

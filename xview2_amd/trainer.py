@@ -14,11 +14,38 @@ from . import dist as xdist
 from .optim import FlatEMA, FlatOptimizer
 
 
+def _mark_last(loader, wanted):
+    """(index, batch, this is the epoch's last batch) - known from len(loader), or by looking one batch ahead where there is
+    no len; not wanted (no accumulation): plain enumeration, the mark stays False"""
+    if not wanted:
+        for i, batch in enumerate(loader):
+            yield i, batch, False
+        return
+    try:
+        n = len(loader)
+    except TypeError:
+        n = None
+    if n is not None:
+        for i, batch in enumerate(loader):
+            yield i, batch, i == n - 1
+        return
+    it = iter(loader)
+    try:
+        ahead = next(it)
+    except StopIteration:
+        return
+    i = 0
+    for nxt in it:
+        yield i, ahead, False
+        ahead, i = nxt, i + 1
+    yield i, ahead, True
+
+
 class Trainer:
     def __init__(self, gpus=1, precision=32, max_epochs=1, min_epochs=None, sync_batchnorm=False, accelerator=None,
                  default_root_dir=".", resume_from_checkpoint=None, checkpoint_callback=True, callbacks=None,
                  benchmark=True, deterministic=False, num_sanity_val_steps=0, logger=False, log_every=0,
-                 gradient_clip_val=0.0, skip_nonfinite=False, ema_decay=0.0):
+                 gradient_clip_val=0.0, skip_nonfinite=False, ema_decay=0.0, accumulate_grad_batches=1):
         self.gpus, self.max_epochs, self.root = gpus, max_epochs, default_root_dir
         # PL's gradient_clip_val (global-norm clipping, 0 = off) and the step skipping of its native-AMP GradScaler: the flat
         # optimizer's gradient guard (optim.FlatOptimizer.set_guard).  guard_log: one dict per epoch when a guard is set.
@@ -27,6 +54,13 @@ class Trainer:
         # > 0: an exponential moving average of the weights (optim.FlatEMA), updated after every optimizer step; validation, the
         # score that selects best.ckpt and the checkpoints' ema_state_dict are taken from it.  0: off, nothing changes.
         self.ema_decay, self.ema = float(ema_decay), None
+        # PL's accumulate_grad_batches: K consecutive batches of an epoch form a group whose mean gradient takes ONE optimizer
+        # step (optim.FlatOptimizer.accumulate); the epoch's last group may be short and steps with the mean of what it holds.
+        # No group spans an epoch, validation or a checkpoint.  1: off, nothing changes.
+        k = accumulate_grad_batches
+        if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+            raise ValueError("accumulate_grad_batches = %r: must be an integer >= 1" % (k,))
+        self.accumulate_grad_batches = k
         self.sync_batchnorm, self.resume = sync_batchnorm, resume_from_checkpoint
         self.checkpointing = bool(checkpoint_callback)
         self.log_every = log_every
@@ -63,8 +97,9 @@ class Trainer:
         start_epoch, ckpt = 0, None
         # the loader (dataset index, worker pool, sampler) is built once; its length is this rank's steps per epoch
         train_loader = datamodule.train_dataloader()
+        K = self.accumulate_grad_batches
         try:
-            model.steps_per_epoch_hint = len(train_loader)
+            model.steps_per_epoch_hint = -(-len(train_loader) // K)      # optimizer steps: the schedule's warm-up epochs stay epochs
         except TypeError:
             model.steps_per_epoch_hint = None
         opt_cfg = model.configure_optimizers()
@@ -91,6 +126,8 @@ class Trainer:
             if not flat:
                 raise RuntimeError("gradient_clip_val / skip_nonfinite need a flat optimizer (xview2_amd.optim)")
             optimizer.set_guard(self.gradient_clip_val, self.skip_nonfinite)
+        if K > 1 and not flat:
+            raise RuntimeError("accumulate_grad_batches = %d needs a flat optimizer (xview2_amd.optim)" % K)
         self.ema = None
         if self.ema_decay > 0.0:
             if not flat:
@@ -108,12 +145,16 @@ class Trainer:
             model.train()
             if hasattr(train_loader, "set_epoch"):
                 train_loader.set_epoch(epoch)        # DistributedSampler reshuffles per epoch (PL's ddp does this)
-            for i, batch in enumerate(train_loader):
+            for i, batch, last in _mark_last(train_loader, K > 1):
+                closes = K == 1 or last or (i + 1) % K == 0       # this batch ends its group: the optimizer steps
                 optimizer.zero_grad()
                 if reducer:
-                    reducer.prepare()
+                    reducer.prepare(sync=closes)
                 loss = model.training_step(batch, i)
                 loss.backward()
+                if not closes:
+                    optimizer.accumulate()
+                    continue
                 if flat:
                     optimizer.step(reducer.finish())
                     if self.ema is not None:
@@ -132,6 +173,10 @@ class Trainer:
                     frozen = True
                 if self.log_every and self.rank == 0 and self.global_step % self.log_every == 0:
                     print("epoch %d step %d loss %.5f" % (epoch, self.global_step, float(loss)))
+            if flat and optimizer.pending:
+                # (a loader that yields fewer batches than its len never shows its last one: no group may outlive the epoch)
+                raise RuntimeError("epoch %d ended with %d micro-batches of an open accumulation group: the loader yielded fewer "
+                                   "batches than its len()" % (epoch, optimizer.pending))
             xdist.check_peer_exchange()          # one-shot SyncBatchNorm exchange: a timed-out exchange is an error, per epoch
             if guarded:
                 self._report_guard(model, optimizer, epoch, seen)
