@@ -1100,6 +1100,35 @@ int xv2_split_seed(const uint8_t* mask, int B, int H, int W, int r2, void* works
 int xv2_split_grow(const uint8_t* mask, int B, int H, int W, int sweeps, void* workspace, int32_t* pending, void* stream);
 int xv2_split_finish(const uint8_t* mask, int B, int H, int W, void* workspace, uint8_t* out, int32_t* labels, void* stream);
 
+/* ---- register the post image to the pre image (align.hip, xview2_amd/utils/align.py) ---------------------------------------
+ * An integer translation found by block matching.  All quantities are integers.
+ * Luma.  Scenes are uint8 [B][H][W][3] in stored channel order (B, G, R).  Y = (29 c0 + 150 c1 + 77 c2 + 128) >> 8, in 0..255.
+ * Search.  R is the radius, 1 <= R <= 32, D = 2R + 1.  H > 2R, W > 2R, H * W < 2^30 and B <= 65535 are required.  The interior
+ * is I = [R, H - R) x [R, W - R): for every p in I and every shift d = (dy, dx) with |dy|, |dx| <= R the pixel p + d lies inside
+ * the image, so no padding rule enters the estimate and every shift is summed over the same pixels.
+ * Tiles.  T in {32, 64, 128}.  Tile (by, bx) holds the rows R + by T ... min(R + (by + 1) T, H - R) - 1 and the columns
+ * likewise; nby = ceil((H - 2R) / T), nbx = ceil((W - 2R) / T); edge tiles are partial.
+ * Tables.  S_b(d) = the sum over p in tile b of |Ypre(p) - Ypost(p + d)|, at most 255 T^2 < 2^22 (uint32), and
+ * S(d) = the sum of S_b(d) over the tiles, below 2^38 (int64).  Tables are indexed [dy + R][dx + R].
+ * Best shift of a table.  The smallest S wins; ties go to the smallest dy^2 + dx^2, then the smallest dy, then the smallest dx.
+ * A table whose entries are all equal (no texture) therefore gives (0, 0).  The best shift d aligns post(p + d) with pre(p).
+ * Resampling.  out[b][y][x][:] = src[b][tri(y + dy, H)][tri(x + dx, W)][:] with tri the reflection of the scene section below,
+ * extended to negative indices by floor modulo (m = i mod 2 (L - 1); m < L ? m : 2 (L - 1) - m; tri(i, 1) = 0): every int32
+ * shift is defined, and the near side reflects as np.pad(mode="reflect") does.
+ * xv2_align_estimate: block_sad uint32 [B][nby][nbx][D][D], sad int64 [B][D][D], block_shift int32 [B][nby][nbx][2] and shift
+ * int32 [B][2], both as (dy, dx).  Three launches; nothing is read back between them.  Every table entry is written once with
+ * a plain store and every sum is an integer sum, so the same input gives the same bytes on every run and stream.  The
+ * workspace (xv2_align_workspace bytes, 0 outside the limits above; 16-byte aligned; needs no clearing) holds int64 partial
+ * sums over chunks of 32 tiles.  Outputs must be aligned to their element size; the scenes may have any alignment.
+ * xv2_translate_u8: src, out uint8 [B][H][W][C], 1 <= C <= 8, H * W < 2^30, B <= 65535; shift is the DEVICE array int32 [B][2]
+ * the estimate wrote (or any other), so estimate followed by translate needs no host round trip; out must not overlap src.
+ * No input is written, nothing is written outside the outputs and the workspace, and a bad argument is XV2_EINVAL before
+ * anything is enqueued. */
+size_t xv2_align_workspace(int B, int H, int W, int R, int T);
+int xv2_align_estimate(const uint8_t* pre, const uint8_t* post, int B, int H, int W, int R, int T, void* workspace,
+                       uint32_t* block_sad, int64_t* sad, int32_t* block_shift, int32_t* shift, void* stream);
+int xv2_translate_u8(const uint8_t* src, int B, int H, int W, int C, const int32_t* shift, uint8_t* out, void* stream);
+
 /* ---- scene inference: windows of a scene of any size, blended on the device (xview2_amd/scene.py, scene.hip) ---------
  * A scene is H x W pixels, H * W < 2^30.  Windows are h x w (multiples of 32, 32..2048) with their origins (y0, x0) in a
  * device table; the table's order is the summation order.  tri(i, L) is reflection without repeating the edge, iterated:

@@ -2758,3 +2758,55 @@ def split_buildings(mask, r2, sweeps_per_call=8, return_labels=False):
     labels = torch.empty((B, H, W), dtype=torch.int32, device=mask.device) if return_labels else None
     call("xv2_split_finish", mask, B, H, W, ws, out, labels)
     return (out, calls, labels) if return_labels else (out, calls)
+
+
+# ---- register the post image to the pre image (csrc/align.hip) ------------------------------------------------------------
+def _align_scene(what, name, t):
+    _need_cuda(t)
+    if t.dim() != 4 or t.shape[3] != 3 or t.dtype != torch.uint8:
+        raise ValueError("%s: %s must be uint8 [B,H,W,3], got %s %s" % (what, name, t.dtype, tuple(t.shape)))
+    return t.contiguous()
+
+
+def align_estimate(pre_u8, post_u8, radius, tile=128):
+    """Sums of absolute luma differences between pre(p) and post(p + d) over every shift |dy|, |dx| <= radius, per tile of
+    tile x tile interior pixels and over the whole interior, and the best shift of each (include/xv2.h, "register the post
+    image to the pre image").  pre_u8, post_u8: uint8 [B,H,W,3] device scenes of one shape.  Returns device tensors
+    (block_sad int32 [B,nby,nbx,D,D] - the uint32 table, whose entries stay below 2^22 -, sad int64 [B,D,D], block_shift int32
+    [B,nby,nbx,2], shift int32 [B,2]); shifts are (dy, dx).  Nothing is read back."""
+    pre_u8 = _align_scene("align_estimate", "pre", pre_u8)
+    post_u8 = _align_scene("align_estimate", "post", post_u8)
+    if pre_u8.shape != post_u8.shape or pre_u8.device != post_u8.device:
+        raise ValueError("align_estimate: pre %s and post %s differ" % (tuple(pre_u8.shape), tuple(post_u8.shape)))
+    B, H, W, _ = (int(v) for v in pre_u8.shape)
+    R, T = int(radius), int(tile)
+    need = int(query("xv2_align_workspace", B, H, W, R, T))
+    if need == 0:
+        raise ValueError("align_estimate: B=%d H=%d W=%d radius=%d tile=%d outside the supported sizes (radius 1..32, tile 32, "
+                         "64 or 128, H and W above 2 * radius, H*W < 2^30, B <= 65535)" % (B, H, W, R, T))
+    D, nby, nbx = 2 * R + 1, -(-(H - 2 * R) // T), -(-(W - 2 * R) // T)
+    dev = pre_u8.device
+    block_sad = torch.empty((B, nby, nbx, D, D), dtype=torch.int32, device=dev)
+    sad = torch.empty((B, D, D), dtype=torch.int64, device=dev)
+    block_shift = torch.empty((B, nby, nbx, 2), dtype=torch.int32, device=dev)
+    shift = torch.empty((B, 2), dtype=torch.int32, device=dev)
+    call("xv2_align_estimate", pre_u8, post_u8, B, H, W, R, T, _ws(need, pre_u8), block_sad, sad, block_shift, shift)
+    return block_sad, sad, block_shift, shift
+
+
+def translate_u8(src, shift):
+    """out[b][y][x][:] = src[b][tri(y + dy, H)][tri(x + dx, W)][:] with (dy, dx) = shift[b]: src uint8 [B,H,W,C], 1 <= C <= 8,
+    shift int32 [B,2] ON THE DEVICE (what align_estimate returned, so no host round trip lies between the two).  The
+    reflection does not repeat the edge (np.pad(mode="reflect")) and is defined for every int32 shift."""
+    _need_cuda(src)
+    if src.dim() != 4 or src.dtype != torch.uint8 or not 1 <= src.shape[3] <= 8:
+        raise ValueError("translate_u8: src must be uint8 [B,H,W,C] with 1 <= C <= 8, got %s %s" % (src.dtype, tuple(src.shape)))
+    B, H, W, C = (int(v) for v in src.shape)
+    if not torch.is_tensor(shift) or shift.dtype != torch.int32 or tuple(shift.shape) != (B, 2) or shift.device != src.device:
+        raise ValueError("translate_u8: shift must be an int32 [%d,2] tensor on %s" % (B, src.device))
+    if H * W >= 1 << 30 or B > 65535:
+        raise ValueError("translate_u8: B=%d H=%d W=%d outside the supported sizes (H*W < 2^30, B <= 65535)" % (B, H, W))
+    src = src.contiguous()
+    out = torch.empty_like(src)
+    call("xv2_translate_u8", src, B, H, W, C, shift.contiguous(), out)
+    return out

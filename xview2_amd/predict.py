@@ -12,7 +12,9 @@ damage class, pixel counts, confidence) and <stem>_buildings.json (totals), comp
 map (xview2_amd.utils.polygons), with the table's row as properties; it implies --buildings.  --simplify T
 reduces those outlines by Douglas-Peucker with a tolerance of T pixels, on the GPU; it changes the GeoJSON only.  --split R cuts the localization
 map where buildings touch (xview2_amd.utils.split) before any of these outputs is made: the PNGs, the table and the outlines
-all come from the split maps."""
+all come from the split maps.  --align R registers the post scene to the pre scene first (xview2_amd.utils.align): the
+best whole-pixel translation within R pixels is found and applied on the GPU before the damage model sees the pair, and
+<stem>_alignment.json reports the shift, the residuals and how far the tiles of the scene agree with it."""
 import os
 from argparse import ArgumentDefaultsHelpFormatter, ArgumentParser
 
@@ -46,6 +48,12 @@ def get_parser():
         "pixels of what is left (Douglas-Peucker per ring, 0 <= T < 4096); 0 = off.  No value is recommended")
     arg("--split", type=int, default=0, metavar="R", help="cut buildings that touch: erosion radius in pixels, 0 = off; applied "
         "after --dilate (a dilation after it would close the cuts again) and before the vote of --components")
+    arg("--align", type=int, default=0, metavar="R", help="register the post scene to the pre scene before the damage model "
+        "reads the pair: the best whole-pixel translation with |dy|, |dx| <= R (1..32) is applied to the post scene and "
+        "<stem>_alignment.json is written; 0 = off.  A shift found at the limit R (at_limit in the report) means the true "
+        "offset may be larger than the search.  Needs --post.  No radius is recommended")
+    arg("--align_tile", type=int, default=128, choices=[32, 64, 128], help="with --align: side of the tiles whose own best "
+        "shifts the report lists")
     return parser
 
 
@@ -85,6 +93,11 @@ def _load(path, ema, tta, device):
 
 def main(argv=None):
     args = get_parser().parse_args(argv)
+    if args.align:
+        from .utils.align import check_radius
+        check_radius(args.align)
+        if args.post is None:
+            raise ValueError("--align needs --post")
     if args.ckpt_loc is None and args.ckpt_dmg is None:
         raise ValueError("give --ckpt_loc, --ckpt_dmg or both")
     if args.ckpt_dmg is not None and args.post is None:
@@ -97,7 +110,7 @@ def main(argv=None):
     if args.simplify:
         from .utils.polygons import quantise_tolerance
         quantise_tolerance(args.simplify)
-    pairs = pair_inputs(args.pre, args.post if args.ckpt_dmg is not None else None)
+    pairs = pair_inputs(args.pre, args.post if args.ckpt_dmg is not None or args.align else None)
     if not torch.cuda.is_available():
         raise RuntimeError("xview2_amd.predict runs on the MI355X only; there is no CPU fallback")
     device = torch.device("cuda", torch.cuda.current_device())
@@ -124,6 +137,11 @@ def main(argv=None):
         pre_d = torch.from_numpy(pre).to(device)
         post_d = torch.from_numpy(post).to(device) if post is not None else None
         H, W, _ = pre.shape
+        if args.align:
+            from .utils import align
+            post_d, info = scene.align_pair(pre_d, post_d, args.align, args.align_tile)
+            with open(stem + "_alignment.json", "w") as f:
+                f.write(align.dumps(align.report_of(info, H, W)))
         loc_maps = loc.predict(pre_d) if loc is not None else None
         dmg_maps = dmg.predict(pre_d, post_d) if dmg is not None else None
         # a missing partner is neutral in the fusion: every pixel a building / no pixel damaged beyond class 1

@@ -120,6 +120,24 @@ def _check_scene(name, t):
     return t.contiguous()
 
 
+def align_pair(pre_u8, post_u8, radius, tile=128):
+    """Register post to pre by the best whole-pixel translation within `radius` (include/xv2.h, "register the post image to
+    the pre image"; utils/align.py): uint8 [H, W, 3] device scenes -> (post resampled by the global shift, info).  The shift
+    goes from the estimate to the resampler on the device; info holds the estimate's device tables (block_sad, sad,
+    block_shift, shift, each with a leading batch axis of 1) and radius / tile - utils.align.report_of(info, H, W) reads them
+    back into the report."""
+    from . import ops
+    from .utils.align import check_radius, check_tile
+    radius, tile = check_radius(radius), check_tile(tile)
+    pre_u8, post_u8 = _check_scene("pre", pre_u8), _check_scene("post", post_u8)
+    if post_u8.shape != pre_u8.shape or post_u8.device != pre_u8.device:
+        raise ValueError("pre %s and post %s scenes differ" % (tuple(pre_u8.shape), tuple(post_u8.shape)))
+    block_sad, sad, block_shift, shift = ops.align_estimate(pre_u8[None], post_u8[None], radius, tile)
+    aligned = ops.translate_u8(post_u8[None], shift)[0]
+    return aligned, {"radius": radius, "tile": tile, "block_sad": block_sad, "sad": sad, "block_shift": block_shift,
+                     "shift": shift}
+
+
 class ScenePredictor:
     """model: a lightning.Model in eval mode (its forward is called, so --tta works as in eval), or any callable
     DeviceImage -> fp32 logits [K, C, window, window].  kind: one of SIGMOID1 / SOFTMAX / SIGMOID / RELU; by default what
