@@ -1155,6 +1155,35 @@ int xv2_scene_blend(const float* logits, int kind, int C, const int32_t* origins
  * (scene.axis_normaliser); their product is below 2^24. */
 int xv2_scene_finalize(float* acc, int Cout, int H, int W, const int32_t* wy, const int32_t* wx, void* stream);
 
+/* ---- resize a device scene and bring its maps back (resize.hip, xview2_amd/resize.py, scene.py predict(scales=...)) --------
+ * The separable resampler of Pillow (libImaging/Resample.c).  Per axis in -> out: scale = in / out, filterscale =
+ * max(scale, 1), support = base * filterscale with base 2 (bicubic, a = -0.5) or 1 (bilinear, the triangle); output i has
+ * center = (i + 0.5) scale, start = max((int)(center - support + 0.5), 0), count = min((int)(center + support + 0.5), in) -
+ * start, weights filter((start + j - center + 0.5) / filterscale) summed in index order and divided by that sum, all in fp64.
+ * ceil(support) * 2 + 1 coefficient slots.  Limits: per axis out <= 4 in and in <= 4 out, so at most 17 (bicubic) / 9
+ * (bilinear) slots; both images below 2^30 pixels.  The HOST builds the tables (xview2_amd/resize.py); xtab / ytab are device
+ * arrays int32 [w | h][2 + slots] with rows {start, count, k[slots]}, unused slots zero.  An axis that keeps its size carries
+ * the identity table {i, 1, one}: the same values as a skipped pass.  Horizontal pass first.  One launch each on `stream`, no
+ * workspace, no intermediate in device memory.  Every table-derived index is clamped into the image.  No input is written,
+ * nothing is written outside dst, dst must not overlap src, and a bad argument is XV2_EINVAL before anything is enqueued.
+ * xv2_resize_u8: uint8 [H][W][C] -> [h][w][C], C = 1, 3 or 6, exactly Image.resize((w, h), Image.BICUBIC): k is the weight in
+ * 22-bit fixed point, (int)(+-0.5 + weight * 2^22), and each pass ends in the uint8 round-and-clip
+ * clip8((2^21 + sum_j s[start + j] k[j]) >> 22), int32 sums.
+ * xv2_resize_f32: fp32 planar [C][Hs][Ws] -> [C][H][W], 1 <= C <= 8, bilinear (no negative weight: an average of
+ * probabilities stays inside the range of its inputs up to rounding).  k holds the bits of the fp32 nearest the fp64 weight.
+ * r = k[0] s[start]; r = r + k[j] s[start + j] for j = 1 .. count - 1: every product and every sum rounded to fp32 on its
+ * own, in tap order, the intermediate between the passes fp32.  mode: WRITE dst = r; ACCUMULATE dst = dst + r; FINISH
+ * dst = (dst + r) / (float)k, an fp32 division, k = 1..8 the number of maps in the average (read in that mode only). */
+#define XV2_RESIZE_U8_TAPS  17
+#define XV2_RESIZE_F32_TAPS 9
+#define XV2_RESIZE_WRITE      0
+#define XV2_RESIZE_ACCUMULATE 1
+#define XV2_RESIZE_FINISH     2
+int xv2_resize_u8(const uint8_t* src, int H, int W, int C, const int32_t* xtab, const int32_t* ytab, int h, int w, uint8_t* dst,
+                  void* stream);
+int xv2_resize_f32(const float* src, int C, int Hs, int Ws, const int32_t* xtab, const int32_t* ytab, int H, int W, int mode,
+                   int k, float* dst, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2810,3 +2810,66 @@ def translate_u8(src, shift):
     out = torch.empty_like(src)
     call("xv2_translate_u8", src, B, H, W, C, shift.contiguous(), out)
     return out
+
+
+# ---- resize a device scene and bring its maps back (csrc/resize.hip, xview2_amd/resize.py) -------------------------------------
+RESIZE_MODES = {"write": 0, "accumulate": 1, "finish": 2}      # include/xv2.h XV2_RESIZE_*
+
+
+def _axis_tables(builder, in_h, in_w, out_h, out_w, device):
+    """(xtab, ytab) on the device: ONE upload of the two host tables (the limits are checked by the builder: ValueError)"""
+    import numpy as np
+    xt, yt = builder(in_w, out_w), builder(in_h, out_h)
+    both = torch.from_numpy(np.concatenate((xt.ravel(), yt.ravel()))).to(device)
+    return both[:xt.size], both[xt.size:]
+
+
+def resize_u8(img, h, w):
+    """Pillow's Image.resize((w, h), Image.BICUBIC) of a uint8 [H,W,C] device image, C = 1, 3 or 6, bit for bit: antialiased
+    when down-scaling, per axis out <= 4 in and in <= 4 out (include/xv2.h, "resize a device scene").  -> uint8 [h,w,C]"""
+    from . import resize
+    _need_cuda(img)
+    if img.dim() != 3 or img.dtype != torch.uint8 or img.shape[2] not in (1, 3, 6):
+        raise ValueError("resize_u8: img must be uint8 [H,W,C] with C = 1, 3 or 6, got %s %s" % (img.dtype, tuple(img.shape)))
+    H, W, C = (int(v) for v in img.shape)
+    h, w = int(h), int(w)
+    xtab, ytab = _axis_tables(resize.axis_table_u8, H, W, h, w, img.device)
+    if H * W >= 1 << 30 or h * w >= 1 << 30:
+        raise ValueError("resize_u8: %d x %d -> %d x %d exceeds 2^30 pixels per image" % (H, W, h, w))
+    img = img.contiguous()
+    out = torch.empty((h, w, C), dtype=torch.uint8, device=img.device)
+    call("xv2_resize_u8", img, H, W, C, xtab, ytab, h, w, out)
+    return out
+
+
+def resize_f32(maps, H, W, out=None, mode="write", k=None):
+    """Planar fp32 maps [C,Hs,Ws], 1 <= C <= 8, resampled to [C,H,W] with the bilinear (triangle) filter in the exact fp32 rule
+    of include/xv2.h ("resize a device scene"; the numpy float32 restatement in tests/resize_ref.py gives the same bits).
+    mode "write": out = r (out may be None: a new tensor); "accumulate": out = out + r; "finish": out = (out + r) / k, an
+    fp32 division by the number k of maps in the average.  -> out"""
+    from . import resize
+    _need_cuda(maps)
+    if maps.dim() != 3 or maps.dtype != torch.float32 or not 1 <= maps.shape[0] <= 8:
+        raise ValueError("resize_f32: maps must be fp32 [C,Hs,Ws] with 1 <= C <= 8, got %s %s" % (maps.dtype, tuple(maps.shape)))
+    if mode not in RESIZE_MODES:
+        raise ValueError("resize_f32: mode %r is none of %s" % (mode, sorted(RESIZE_MODES)))
+    C, Hs, Ws = (int(v) for v in maps.shape)
+    H, W = int(H), int(W)
+    if mode == "finish":
+        if k is None or int(k) != k or not 1 <= int(k) <= resize.MAX_SCALES:
+            raise ValueError("resize_f32: mode 'finish' needs k = 1..%d, the number of maps in the average, got %r" % (
+                resize.MAX_SCALES, k))
+    elif k is not None:
+        raise ValueError("resize_f32: k belongs to mode 'finish' only")
+    xtab, ytab = _axis_tables(resize.axis_table_f32, Hs, Ws, H, W, maps.device)
+    if Hs * Ws >= 1 << 30 or H * W >= 1 << 30:
+        raise ValueError("resize_f32: %d x %d -> %d x %d exceeds 2^30 pixels per map" % (Hs, Ws, H, W))
+    if out is None:
+        if mode != "write":
+            raise ValueError("resize_f32: mode %r adds to out, which is missing" % mode)
+        out = torch.empty((C, H, W), dtype=torch.float32, device=maps.device)
+    elif (not torch.is_tensor(out) or out.dtype != torch.float32 or tuple(out.shape) != (C, H, W) or out.device != maps.device
+          or not out.is_contiguous()):
+        raise ValueError("resize_f32: out must be a contiguous fp32 [%d,%d,%d] tensor on %s" % (C, H, W, maps.device))
+    call("xv2_resize_f32", maps.contiguous(), C, Hs, Ws, xtab, ytab, H, W, RESIZE_MODES[mode], int(k) if k is not None else 1, out)
+    return out

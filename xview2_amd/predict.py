@@ -14,7 +14,12 @@ reduces those outlines by Douglas-Peucker with a tolerance of T pixels, on the G
 map where buildings touch (xview2_amd.utils.split) before any of these outputs is made: the PNGs, the table and the outlines
 all come from the split maps.  --align R registers the post scene to the pre scene first (xview2_amd.utils.align): the
 best whole-pixel translation within R pixels is found and applied on the GPU before the damage model sees the pair, and
-<stem>_alignment.json reports the shift, the residuals and how far the tiles of the scene agree with it."""
+<stem>_alignment.json reports the shift, the residuals and how far the tiles of the scene agree with it.  --scales s1,s2,...
+predicts every scene once per scale and averages the maps (xview2_amd.scene, predict(scales=...)): the scene is resized on the
+GPU as Pillow's bicubic resize does it, predicted at that size, and the maps are brought back to the native grid, where the
+post-processing and every output stay; --save_probs writes the averaged maps.  One value other than 1 predicts imagery of
+another ground resolution (a model trained at 0.5 m per pixel reads a 0.3 m scene at --scales 0.6); --align runs before it, at
+the native size."""
 import os
 from argparse import ArgumentDefaultsHelpFormatter, ArgumentParser
 
@@ -54,7 +59,21 @@ def get_parser():
         "offset may be larger than the search.  Needs --post.  No radius is recommended")
     arg("--align_tile", type=int, default=128, choices=[32, 64, 128], help="with --align: side of the tiles whose own best "
         "shifts the report lists")
+    arg("--scales", type=parse_scales, default="1", metavar="S1,S2,...", help="predict every scene once per scale and average "
+        "the maps in this order: 1 to 8 values in [0.25, 4], no duplicates.  The scene is resized on the GPU (bicubic, as "
+        "Pillow), predicted at that size and the maps resampled back (bilinear); all outputs stay on the native grid.  One "
+        "value is a ground-resolution correction: the ratio of the scene's metres per pixel to the training data's.  No "
+        "value is recommended")
     return parser
+
+
+def parse_scales(text):
+    """'0.75,1,1.25' -> (0.75, 1.0, 1.25), checked (resize.check_scales); ValueError for anything else"""
+    from .resize import check_scales
+    parts = [p.strip() for p in str(text).split(",")]
+    if not all(parts):
+        raise ValueError("--scales: an empty entry in %r" % (text,))
+    return check_scales(tuple(float(p) for p in parts))
 
 
 def _listing(path):
@@ -142,8 +161,8 @@ def main(argv=None):
             post_d, info = scene.align_pair(pre_d, post_d, args.align, args.align_tile)
             with open(stem + "_alignment.json", "w") as f:
                 f.write(align.dumps(align.report_of(info, H, W)))
-        loc_maps = loc.predict(pre_d) if loc is not None else None
-        dmg_maps = dmg.predict(pre_d, post_d) if dmg is not None else None
+        loc_maps = loc.predict(pre_d, scales=args.scales) if loc is not None else None
+        dmg_maps = dmg.predict(pre_d, post_d, scales=args.scales) if dmg is not None else None
         # a missing partner is neutral in the fusion: every pixel a building / no pixel damaged beyond class 1
         loc_map = loc_maps[0] if loc is not None else torch.ones((H, W), dtype=torch.float32, device=device)
         dmg_map = (scene.decode_damage(dmg_maps, dmg.kind) if dmg is not None

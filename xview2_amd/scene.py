@@ -19,8 +19,12 @@ The geometry below is integer arithmetic in numpy, importable without a GPU, and
   axis_normaliser(L, n, overlap)  W[p] = the sum of r over the origins covering p.  The grid is a product, so the weight
                                   sum of scene pixel (y, x) is Wy[y] Wx[x] <= 9 * 1025^2 < 2^24: an exact fp32 integer,
                                   and no weight-sum buffer exists on the device.
+  scaled_size(H, W, s)            the size the scene is predicted at under predict(scales=...): round(H s), round(W s), each
+                                  at least 1 (xview2_amd/resize.py, with the coefficient tables of the two resize kernels).
 """
 import numpy as np
+
+from .resize import check_scales, scaled_size  # noqa: F401  (the geometry of predict(scales=...))
 
 SIGMOID1, SOFTMAX, SIGMOID, RELU = 0, 1, 2, 3      # include/xv2.h XV2_SCENE_*
 MAX_WINDOWS = 1024                                  # XV2_SCENE_MAX_WINDOWS: windows per kernel call
@@ -155,10 +159,14 @@ class ScenePredictor:
             raise ValueError("ScenePredictor: unknown kind %r" % (kind,))
         self.model, self.window, self.overlap, self.batch, self.kind = model, window, overlap, batch, kind
 
-    def predict(self, pre_u8, post_u8=None):
-        """uint8 [H, W, 3] device scene(s) in stored (BGR) channel order -> fp32 [Cout, H, W] blended maps on the device"""
-        import torch
-        from . import ops
+    def predict(self, pre_u8, post_u8=None, scales=(1.0,)):
+        """uint8 [H, W, 3] device scene(s) in stored (BGR) channel order -> fp32 [Cout, H, W] blended maps on the device.
+
+        scales: the scene is predicted once per scale s, in list order - resized to scaled_size(H, W, s) as Pillow's bicubic
+        resize does it (ops.resize_u8), predicted window by window at that size (a scaled scene smaller than the window takes
+        the reflect padding), and the maps brought back to H x W with the bilinear resample of ops.resize_f32 - and the
+        result is ((r1 + r2) + ... + rk) / k in fp32.  A scale of 1 contributes the maps as they are.  1 to 8 scales in
+        [0.25, 4] without duplicates; scales=(1,) is the plain prediction, the same calls and the same bits."""
         pre_u8 = _check_scene("pre", pre_u8)
         if post_u8 is not None:
             post_u8 = _check_scene("post", post_u8)
@@ -167,6 +175,37 @@ class ScenePredictor:
         H, W, _ = pre_u8.shape
         if H * W >= 1 << 30:
             raise ValueError("scene %d x %d exceeds 2^30 pixels" % (H, W))
+        scales = check_scales(scales)
+        if scales == (1.0,):
+            return self._predict_native(pre_u8, post_u8)
+        from . import ops, resize
+        sizes = [scaled_size(H, W, s) for s in scales]
+        for s, (Hs, Ws) in zip(scales, sizes):          # every refusal before the first launch
+            if Hs * Ws >= 1 << 30:
+                raise ValueError("scene %d x %d at scale %g is %d x %d: 2^30 pixels or more" % (H, W, s, Hs, Ws))
+            resize.check_axis(H, Hs)
+            resize.check_axis(W, Ws)
+        k, acc = len(scales), None
+        for i, (s, (Hs, Ws)) in enumerate(zip(scales, sizes)):
+            if s == 1.0:
+                maps = self._predict_native(pre_u8, post_u8)
+            else:
+                maps = self._predict_native(ops.resize_u8(pre_u8, Hs, Ws),
+                                            ops.resize_u8(post_u8, Hs, Ws) if post_u8 is not None else None)
+            if i == 0:
+                # the first term as it is: the predictor's own tensor at scale 1, else a plain write
+                acc = maps if s == 1.0 else ops.resize_f32(maps, H, W)
+            elif i < k - 1:
+                ops.resize_f32(maps, H, W, out=acc, mode="accumulate")      # (scale 1: the identity tables, acc + maps)
+            else:
+                ops.resize_f32(maps, H, W, out=acc, mode="finish", k=k)
+        return acc
+
+    def _predict_native(self, pre_u8, post_u8):
+        """the windowed prediction of checked scenes at the size they have"""
+        import torch
+        from . import ops
+        H, W, _ = pre_u8.shape
         n, dev = self.window, pre_u8.device
         origins = torch.from_numpy(scene_windows(H, W, n, self.overlap)).to(dev)
         wy = torch.from_numpy(axis_normaliser(H, n, self.overlap)).to(dev)
