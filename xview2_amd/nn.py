@@ -63,10 +63,11 @@ class bn_split:
 FUSED_INFERENCE = True     # eval + no_grad: one launch per conv layer (tests switch it off to compare both forms)
 
 
-def conv_bn_act(conv, bn, x0, x1=None, act=ops.ACT_NONE, residual=None, passthrough=False):
+def conv_bn_act(conv, bn, x0, x1=None, act=ops.ACT_NONE, residual=None, passthrough=False, want_gap=False):
     """act(BN(conv(cat(x0, x1))) [+ residual]) - one fused autograd node.  passthrough=True (or 1) returns (out, x0 alias):
     hand the alias to x0's other consumer and the two gradients are summed inside the backward-data kernel; 2 = alias of x1,
-    3 = (out, x0 alias, x1 alias)."""
+    3 = (out, x0 alias, x1 alias).  want_gap: the output's only consumer is split attention, so a training-mode node may leave
+    the global average pool's partial sums behind for it (ops.ConvBnActFn.forward); inference ignores it."""
     passthrough = int(passthrough) & (3 if x1 is not None else 1)
     if not bn.training and not torch.is_grad_enabled() and x0.is_cuda and FUSED_INFERENCE:
         # inference: BatchNorm folded into the convolution epilogue (xv2_conv2d_forward_fused), no autograd node
@@ -75,7 +76,7 @@ def conv_bn_act(conv, bn, x0, x1=None, act=ops.ACT_NONE, residual=None, passthro
     bump_bn_counter(bn)
     bs = ops.BnState(bn, SYNC_BN)
     out = ops.ConvBnActFn.apply(x0, x1, conv._parameters["weight"], bs.weight, bs.bias, residual, _cfg(conv),
-                                bs, act, bn.training, passthrough)
+                                bs, act, bn.training, passthrough, want_gap)
     if passthrough == 3:
         ops.carry_amax(x0, out[1])
         ops.carry_amax(x1, out[2])

@@ -227,6 +227,19 @@ def _tok_ptr(tok):
     return tok[0] if (tok is not None and tok[3].gen[tok[1]] == tok[2]) else None
 
 
+def _src_amax(x0, x1):
+    """what a convolution node reads off its sources: ((token of x0's maximum, of x1's), is x0 a transposed convolution's
+    output - its backward then wants the maximum of the gradient sent back)"""
+    return ((getattr(x0, "_xv2_amax", None), getattr(x1, "_xv2_amax", None) if x1 is not None else None),
+            bool(getattr(x0, "_xv2_convT_out", False)))
+
+
+def _amax_ptrs(am_in, third=None):
+    """the sources' tokens (_src_amax) as slot addresses, with a third entry (the output's token, dy's slots) - the triple a
+    launch's set_amax is fed from; None without tokens"""
+    return (_tok_ptr(am_in[0]), _tok_ptr(am_in[1]), third) if am_in is not None else None
+
+
 def carry_amax(src, alias):
     """a pass-through alias (a Function output that IS one of its inputs) is a new tensor object: hand the source's recorded
     maximum on to it"""
@@ -676,6 +689,17 @@ def _persist(tag, nfloats, device):
     return t
 
 
+_splat_writes = {}      # device index -> how many launches have been handed the "splat" scratch
+
+
+def _splat_scratch(N, hw, C, device):
+    """-> (buffer, stamp): the split-attention scratch for ONE launch that may write it, and that hand-out's number on the
+    device.  A producer keeps the pair as its claim on the contents; the claim holds while nothing else has been handed the
+    buffer since (SplitAttentionFn.forward)."""
+    stamp = _splat_writes[device.index] = _splat_writes.get(device.index, 0) + 1
+    return _persist("splat", query("xv2_splat_gap_workspace", N, hw, C) // 4 + 16, device), stamp
+
+
 def _conv_bn_act_train(x0, x1, weight, g, bn, residual, act, ihwo_out, want_mask, amax=None, want_gap=False, head=None):
     """Training-mode conv + BatchNorm + (residual) + activation of one ungrouped layer as ONE ABI call
     (xv2_conv_bn_act_forward = the three launches of _conv_forward + _bn_forward, same order, same stream).
@@ -734,38 +758,34 @@ def _conv_bn_act_train(x0, x1, weight, g, bn, residual, act, ihwo_out, want_mask
         set_amax(amax[0], amax[1], None, amax[2][0] if amax[2] is not None else None)
         if amax[2] is not None:
             z._xv2_amax = amax[2]
+    # the arguments the three entry points share, from the split-K scratch to the coefficient rows
+    run = (_persist("splitk", (wsb + 3) // 4 + 4, dev) if wsb else None, sums, _stats_scratch(Cout, dev), float(npix),
+           bn.weight, bn.bias, float(bn.eps), float(bn.momentum), bn.running_mean, bn.running_var, blob[0], blob[1], blob[2], blob[3])
+    stats = (blob[0], blob[1], float(npix), blob[2], blob[3])
     if head is not None:
         hw2, hbias, nchw_out = head
         co = hw2.shape[0]
         logits = _f32((N, co, OH, OW) if nchw_out else (N, OH, OW, co), x0)
-        call("xv2_conv_bn_act_head_forward", d, x0, C0t, x1, C1t, ohwi, y, Cout, part,
-             _persist("splitk", (wsb + 3) // 4 + 4, dev) if wsb else None,
-             sums, _stats_scratch(Cout, dev), float(npix), bn.weight, bn.bias, float(bn.eps), float(bn.momentum),
-             bn.running_mean, bn.running_var, blob[0], blob[1], blob[2], blob[3], act, co, hw2, hbias, logits,
+        call("xv2_conv_bn_act_head_forward", d, x0, C0t, x1, C1t, ohwi, y, Cout, part, *run, act, co, hw2, hbias, logits,
              1 if nchw_out else 0, _dt(y))
-        return y, logits, None, (blob[0], blob[1], float(npix), blob[2], blob[3])
+        return y, logits, None, stats
     if G > 1:
         warr = (ctypes.c_void_p * G)(*[pk[0].data_ptr() for pk in packs])
-        gap_part = None
+        gap_part = claim = None
         if (want_gap and G == 2 and residual is None and zmask is None and act == ACT_RELU and
                 query("xv2_bn_act_gap_supported", Cout // 2) == 1):
             # split attention consumes z next (SplAtConv2d): the apply pass leaves the global average pool's column-sum partials
             # in the tail's scratch; the tensor carries the claim to its one consumer (SplitAttentionFn.forward)
-            gap_part = _persist("splat", query("xv2_splat_gap_workspace", N, OH * OW, Cout // 2) // 4 + 16, dev)
-        call("xv2_conv_bn_act_forward_grouped", d, G, x0, C0t, ctypes.addressof(warr), y, Cout, part, tiles,
-             _persist("splitk", (wsb + 3) // 4 + 4, dev) if wsb else None,
-             sums, _stats_scratch(Cout, dev), float(npix), bn.weight, bn.bias, float(bn.eps), float(bn.momentum),
-             bn.running_mean, bn.running_var, blob[0], blob[1], blob[2], blob[3], residual, Cout, act, z, Cout, zmask,
-             gap_part, _dt(y))
-        if gap_part is not None:
-            z._xv2_gap_part = gap_part
-        return y, z, zmask, (blob[0], blob[1], float(npix), blob[2], blob[3])
-    call("xv2_conv_bn_act_forward", d, x0, C0t, x1, C1t, ohwi, y, Cout, part, tiles,
-         _persist("splitk", (wsb + 3) // 4 + 4, dev) if wsb else None,
-         sums, _stats_scratch(Cout, dev), float(npix), bn.weight, bn.bias, float(bn.eps), float(bn.momentum),
-         bn.running_mean, bn.running_var, blob[0], blob[1], blob[2], blob[3], residual, Cout, act, z, Cout, zmask,
-         _dt(y))
-    return y, z, zmask, (blob[0], blob[1], float(npix), blob[2], blob[3])
+            claim = _splat_scratch(N, OH * OW, Cout // 2, dev)
+            gap_part = claim[0]
+        call("xv2_conv_bn_act_forward_grouped", d, G, x0, C0t, ctypes.addressof(warr), y, Cout, part, tiles, *run,
+             residual, Cout, act, z, Cout, zmask, gap_part, _dt(y))
+        if claim is not None:
+            z._xv2_gap_part = claim
+        return y, z, zmask, stats
+    call("xv2_conv_bn_act_forward", d, x0, C0t, x1, C1t, ohwi, y, Cout, part, tiles, *run,
+         residual, Cout, act, z, Cout, zmask, _dt(y))
+    return y, z, zmask, stats
 
 
 def _conv_backward_data(dy, weight, g, in_shape, C0t, C1t, ihwo_packs=None, add_to0=None, add_to1=None, amax_dy=None,
@@ -1218,7 +1238,7 @@ def conv_bn_act_infer(x0, x1, weight, residual, g, bn, act):
     scale, shift = _bn_eval_scale_shift(bn, x0)
     am_in = am_out = None
     if _amax_active(x0) and not (x0.shape[-1] == 4 and x1 is None):      # F16X2 (the RGB stem's image has no recorded maximum)
-        am_in = (_amax_ptr(x0), _amax_ptr(x1))
+        am_in = _amax_ptrs(_src_amax(x0, x1)[0])
         am_out = _amax_new(x0)
     elif _amax_active(x0):
         am_in, am_out = (None, None), _amax_new(x0)
@@ -1230,20 +1250,18 @@ def conv_bn_act_infer(x0, x1, weight, residual, g, bn, act):
 
 
 # ------------------------------------------------------------------------------------------------
-# set by encoders.SplAtConv2d around its conv + bn0 + ReLU call: the layer's output goes to split attention and nowhere else, so
-# its apply pass may leave the global average pool's partial sums behind (xv2_bn_act_gap_forward)
-GAP_REQUEST = False
-
-
+# the convolution nodes: their forward sides read the sources' maxima (_src_amax), their backward sides end in _conv_grads
 class ConvBnActFn(torch.autograd.Function):
     """z = act(BN(conv(cat(x0, x1), W)) [+ residual])  (one autograd node per conv layer)"""
 
     @staticmethod
-    def forward(ctx, x0, x1, weight, gamma, beta, residual, g, bn, act, training, passthrough=False):
+    def forward(ctx, x0, x1, weight, gamma, beta, residual, g, bn, act, training, passthrough=False, want_gap=False):
         """passthrough: also return x0 itself as a second output.  A caller whose x0 has a SECOND consumer (the
         residual shortcut of a bottleneck) feeds that consumer from this alias: its gradient then arrives here and
         the backward-data kernel adds onto it in its epilogue, instead of autograd summing two tensors afterwards.
-        The alias must have exactly one consumer whose gradient tensor is not shared with anybody else."""
+        The alias must have exactly one consumer whose gradient tensor is not shared with anybody else.
+        want_gap (encoders.SplAtConv2d): the output goes to split attention and nowhere else, so the apply pass may leave the
+        global average pool's partial sums behind (xv2_bn_act_gap_forward); z then carries the claim on them."""
         _need_cuda(x0)
         ctx.set_materialize_grads(False)
         passthrough = int(passthrough)          # bit 0: alias of x0, bit 1: alias of x1 (True = 1: x0 only)
@@ -1261,23 +1279,21 @@ class ConvBnActFn(torch.autograd.Function):
         fast = None
         # F16X2: the maxima of the sources (recorded by their producers) and a slot for this layer's output
         am_in = am_out = None
+        ctx.want_dx_amax = False
         # (eval mode too: the fused inference launches record the same maxima in their epilogues - conv_bn_act_infer - so the
         #  two inference paths stay bit-identical)
         if _amax_active(x0):
-            am_in = (getattr(x0_in, "_xv2_amax", None), getattr(x1_in, "_xv2_amax", None) if x1_in is not None else None)
+            am_in, ctx.want_dx_amax = _src_amax(x0_in, x1_in)
             am_out = _amax_new(x0)
         ctx.am_in = am_in
-        # (a source that is a transposed convolution's output: its backward wants the maximum of the gradient sent back)
-        ctx.want_dx_amax = am_in is not None and bool(getattr(x0_in, "_xv2_convT_out", False))
         if LAYER_CALLS and training and ctx.split == 1 and not _sync_group(bn):
-            fast = _conv_bn_act_train(x0, x1, weight, g, bn, residual, act, ctx.ihwo, ctx.has_res,
-                                      (_tok_ptr(am_in[0]), _tok_ptr(am_in[1]), am_out) if am_in is not None else None,
-                                      want_gap=GAP_REQUEST)
+            fast = _conv_bn_act_train(x0, x1, weight, g, bn, residual, act, ctx.ihwo, ctx.has_res, _amax_ptrs(am_in, am_out),
+                                      want_gap=want_gap)
         if fast is not None:
             y, z, zmask, stats = fast
         else:
             y, sums, coeffs = _conv_forward(x0, x1, weight, g, None, want_stats=training, ihwo_out=ctx.ihwo, bn=bn,
-                                            amax_in=(_tok_ptr(am_in[0]), _tok_ptr(am_in[1])) if am_in is not None else None)
+                                            amax_in=_amax_ptrs(am_in))
             if ctx.has_res:
                 z, stats, zmask = _bn_forward(y, residual, act, bn, sums, training, coeffs, want_mask=True, split=ctx.split,
                                               amax_tok=am_out)
@@ -1312,36 +1328,12 @@ class ConvBnActFn(torch.autograd.Function):
         dy, dres, dgamma, dbeta = _bn_backward(dz, z, y, (mean, invstd, ctx.count, scale, shift), gamma, ctx.act,
                                                ctx.bn, ctx.training, ctx.has_res and ctx.needs_input_grad[5],
                                                ctx.split, _amax_new(y) if am_in is not None else None)
-        am_dy = _amax_ptr(dy)
-        dx0 = dx1 = None
-        if ctx.needs_input_grad[0] or (x1 is not None and ctx.needs_input_grad[1]):
-            acc = acc1 = None
-            if dpass is not None and g.groups == 1 and dpass.is_contiguous() and tuple(dpass.shape) == tuple(x0.shape):
-                acc, dpass = dpass, None          # summed inside the backward-data epilogue
-            if (dpass1 is not None and g.groups == 1 and dpass1.is_contiguous() and x1 is not None
-                    and tuple(dpass1.shape) == tuple(x1.shape)):
-                acc1, dpass1 = dpass1, None
-            dx0, dx1 = _conv_backward_data(dy, weight, g, x0.shape[:3], x0.shape[3],
-                                           x1.shape[3] if x1 is not None else 0, ctx.ihwo, acc, acc1, am_dy,
-                                           _amax_new(y) if (ctx.want_dx_amax and am_dy is not None and dpass is None) else None)
-            if dpass is not None:
-                dx0 = dx0 + dpass
-            if dpass1 is not None:
-                dx1 = dx1 + dpass1
-        else:
-            if dpass is not None:
-                dx0 = dpass
-            if dpass1 is not None:
-                dx1 = dpass1
-        ctx.ihwo = None
-        if not ctx.needs_input_grad[2]:
-            dw = None
-        else:
-            wam = (_tok_ptr(am_in[0]), _tok_ptr(am_in[1]), am_dy) if (am_dy is not None and am_in is not None) else None
-            dw = _conv_backward_weight(x0, x1, dy, weight, g, ctx.wparam, wam)
-        ctx.wparam = None
-        return (dx0, dx1, dw, dgamma if ctx.needs_input_grad[3] else None,
-                dbeta if ctx.needs_input_grad[4] else None, dres, None, None, None, None, None)
+        need = ctx.needs_input_grad
+        dx0, dx1, dw = _conv_grads(x0, x1, weight, g, dy, ctx.ihwo, dpass, dpass1, am_in, ctx.want_dx_amax,
+                                   need[0] or (x1 is not None and need[1]), need[2], ctx.wparam)
+        ctx.ihwo = ctx.wparam = None
+        return (dx0, dx1, dw, dgamma if need[3] else None, dbeta if need[4] else None, dres, None, None, None, None, None,
+                None)
 
 
 HEAD_FUSE = os.environ.get("XV2_HEAD_FUSE", "1") != "0"      # the last decoder layer's head inside its BatchNorm passes (include/xv2.h)
@@ -1384,15 +1376,11 @@ class ConvBnActHeadFn(torch.autograd.Function):
         x1 = x1.contiguous() if x1 is not None else None
         need_dx = x0.requires_grad or (x1 is not None and x1.requires_grad)
         ctx.ihwo = [] if need_dx else None
-        am_in = None
-        if _amax_active(x0):      # F16X2: the sources' maxima; no slot for the output - no convolution reads it
-            am_in = (getattr(x0_in, "_xv2_amax", None), getattr(x1_in, "_xv2_amax", None) if x1_in is not None else None)
-        ctx.am_in = am_in
-        ctx.want_dx_amax = am_in is not None and bool(getattr(x0_in, "_xv2_convT_out", False))
+        # F16X2: the sources' maxima; no slot for the output - no convolution reads it
+        ctx.am_in, ctx.want_dx_amax = _src_amax(x0_in, x1_in) if _amax_active(x0) else (None, False)
         co, C = head_weight.shape[0], weight.shape[0]
         w2 = head_weight.reshape(co, C).contiguous()
-        fast = _conv_bn_act_train(x0, x1, weight, g, bn, None, act, ctx.ihwo, False,
-                                  (_tok_ptr(am_in[0]), _tok_ptr(am_in[1]), None) if am_in is not None else None,
+        fast = _conv_bn_act_train(x0, x1, weight, g, bn, None, act, ctx.ihwo, False, _amax_ptrs(ctx.am_in),
                                   head=(w2, head_bias, nchw_out))
         if fast is None:
             raise RuntimeError("ConvBnActHeadFn: no layer-level call for this shape (head_fusable() decides before the node is built)")
@@ -1427,20 +1415,12 @@ class ConvBnActHeadFn(torch.autograd.Function):
             dy._xv2_amax = tok
         call("xv2_bn_act_head_backward", dl, 1 if ctx.nchw else 0, H * W, w2, co, y, C, mean, invstd, gamma, scale, shift,
              ctx.act, float(ctx.count), dy, C, npix, C, sums2, dgamma, dbeta, dhw, dhb, ws, _dt(y))
-        am_dy = _amax_ptr(dy)
-        dx0 = dx1 = None
-        if ctx.needs_input_grad[0] or (x1 is not None and ctx.needs_input_grad[1]):
-            dx0, dx1 = _conv_backward_data(dy, weight, g, x0.shape[:3], x0.shape[3], x1.shape[3] if x1 is not None else 0,
-                                           ctx.ihwo, None, None, am_dy,
-                                           _amax_new(y) if (ctx.want_dx_amax and am_dy is not None) else None)
-        ctx.ihwo = None
-        dw = None
-        if ctx.needs_input_grad[2]:
-            wam = (_tok_ptr(am_in[0]), _tok_ptr(am_in[1]), am_dy) if (am_dy is not None and am_in is not None) else None
-            dw = _conv_backward_weight(x0, x1, dy, weight, g, ctx.wparam, wam)
-        ctx.wparam = None
-        return (dx0, dx1, dw, dgamma if ctx.needs_input_grad[3] else None, dbeta if ctx.needs_input_grad[4] else None,
-                dhw.reshape(ctx.hshape), dhb, None, None, None, None)
+        need = ctx.needs_input_grad
+        dx0, dx1, dw = _conv_grads(x0, x1, weight, g, dy, ctx.ihwo, None, None, am_in, ctx.want_dx_amax,
+                                   need[0] or (x1 is not None and need[1]), need[2], ctx.wparam)
+        ctx.ihwo = ctx.wparam = None
+        return (dx0, dx1, dw, dgamma if need[3] else None, dbeta if need[4] else None, dhw.reshape(ctx.hshape), dhb,
+                None, None, None, None)
 
 
 SHORTCUT_FUSE = os.environ.get("XV2_SHORTCUT_FUSE", "1") != "0"      # the projection shortcut's BatchNorm inside conv3's BatchNorm passes (include/xv2.h)
@@ -1490,19 +1470,18 @@ class BottleneckTailFn(torch.autograd.Function):
         a, x = a.contiguous(), x.contiguous()
         ctx.ihwo3 = [] if a.requires_grad else None
         ctx.ihwod = [] if x.requires_grad else None
-        am_a = am_x = am_out = None
-        active = _amax_active(a)
-        if active:      # F16X2: the sources' maxima and a slot for z
-            am_a, am_x = getattr(a_in, "_xv2_amax", None), getattr(x_in, "_xv2_amax", None)
+        am_out = None
+        ctx.am_a = ctx.am_x = None          # each convolution's sources, as ConvBnActFn keeps them: (token, None)
+        ctx.want_dx_amax = (False, False)
+        if _amax_active(a):      # F16X2: the sources' maxima and a slot for z
+            (ctx.am_a, want_a), (ctx.am_x, want_x) = _src_amax(a_in, None), _src_amax(x_in, None)
+            ctx.want_dx_amax = (want_a, want_x)
             am_out = _amax_new(a)
-        ctx.am_in = (am_a, am_x) if active else None
-        ctx.want_dx_amax = (active and bool(getattr(a_in, "_xv2_convT_out", False)),
-                            active and bool(getattr(x_in, "_xv2_convT_out", False)))
         # the shortcut first, like the two nodes: convolution + statistics + coefficients each, no apply pass
         yd, sums_d, cd = _conv_forward(x, None, w_ds, g_ds, None, want_stats=True, ihwo_out=ctx.ihwod, bn=bn_ds,
-                                       amax_in=(_tok_ptr(am_x), None) if active else None)
+                                       amax_in=_amax_ptrs(ctx.am_x))
         y3, sums_3, c3 = _conv_forward(a, None, w3, g3, None, want_stats=True, ihwo_out=ctx.ihwo3, bn=bn3,
-                                       amax_in=(_tok_ptr(am_a), None) if active else None)
+                                       amax_in=_amax_ptrs(ctx.am_a))
         if cd is None or c3 is None or yd.shape != y3.shape:
             raise RuntimeError("BottleneckTailFn: the statistics did not fold inside the convolution (shortcut_fusable() decides "
                                "before the node is built)")
@@ -1534,9 +1513,8 @@ class BottleneckTailFn(torch.autograd.Function):
         dgammad, dbetad = _grad_like(bn_ds.weight), _grad_like(bn_ds.bias)
         ws = _persist("bnshortcut", (query("xv2_bn_act_shortcut_backward_workspace", npix, C) + 3) // 4 + 4, y3.device)
         dy3, dyd = torch.empty_like(y3), torch.empty_like(yd)
-        am_in = ctx.am_in
         tok3 = tokd = None
-        if am_in is not None:        # F16X2: the apply pass records max |dy3| and max |dy_ds|
+        if ctx.am_a is not None:        # F16X2: the apply pass records max |dy3| and max |dy_ds|
             tok3, tokd = _amax_new(y3), _amax_new(y3)
             if tok3 is not None:
                 set_amax(None, None, None, tok3[0])
@@ -1550,35 +1528,47 @@ class BottleneckTailFn(torch.autograd.Function):
         ctx.wparams = None
         need = ctx.needs_input_grad
         # conv3's gradients, then the shortcut convolution's - the order of the two nodes
-        da, dw3 = _tail_conv_grads(a, w3, ctx.g3, dy3, ctx.ihwo3, None, am_in[0] if am_in is not None else None,
-                                   ctx.want_dx_amax[0], need[0], need[2], w3p)
-        dx, dwd = _tail_conv_grads(x, w_ds, ctx.g_ds, dyd, ctx.ihwod, dpass, am_in[1] if am_in is not None else None,
-                                   ctx.want_dx_amax[1], need[1], need[5], wdp)
+        da, _, dw3 = _conv_grads(a, None, w3, ctx.g3, dy3, ctx.ihwo3, None, None, ctx.am_a, ctx.want_dx_amax[0], need[0],
+                                 need[2], w3p)
+        dx, _, dwd = _conv_grads(x, None, w_ds, ctx.g_ds, dyd, ctx.ihwod, dpass, None, ctx.am_x, ctx.want_dx_amax[1], need[1],
+                                 need[5], wdp)
         ctx.ihwo3 = ctx.ihwod = None
         return (da, dx, dw3, dgamma3 if need[3] else None, dbeta3 if need[4] else None, dwd, dgammad if need[6] else None,
                 dbetad if need[7] else None, None, None, None, None, None, None)
 
 
-def _tail_conv_grads(x0, weight, g, dy, ihwo, dpass, am_x0, want_dx_amax, need_dx, need_dw, wparam):
-    """input and weight gradient of one single-source convolution of BottleneckTailFn, the way ConvBnActFn.backward takes them:
-    `dpass` (the gradient of the pass-through alias) is summed inside the backward-data epilogue where its layout allows"""
-    am_dy = _amax_ptr(dy)
-    dx0 = None
+def _addable(dpass, shape, dtype):
+    """THE rule for summing a pass-through alias's gradient in place: a kernel can add onto `dpass` only if it is laid out like
+    the gradient the kernel would otherwise write - contiguous, that shape, that element type"""
+    return dpass is not None and dpass.is_contiguous() and tuple(dpass.shape) == tuple(shape) and dpass.dtype == dtype
+
+
+def _conv_grads(x0, x1, weight, g, dy, ihwo, dpass0, dpass1, am_in, want_dx_amax, need_dx, need_dw, wparam):
+    """-> (dx0, dx1, dw): the gradients of ONE convolution, the tail of every convolution node's backward.
+    dpass0 / dpass1: gradients of the sources' pass-through aliases (ConvBnActFn.forward) - summed inside the backward-data
+    epilogue where an ungrouped kernel can add onto them (_addable), added afterwards otherwise, and returned as they are when no
+    input gradient is wanted.  am_in: the sources' tokens (_src_amax) or None - without them neither kernel is told a maximum,
+    whatever dy carries (ConvFn).  want_dx_amax: record max |dx0| - possible only where the launch writes the final dx0.
+    ihwo: the backward-data weight packs of the forward pass, or None."""
+    am_dy = _amax_ptr(dy) if am_in is not None else None
+    dx0, dx1 = dpass0, dpass1
     if need_dx:
-        acc = None
-        if dpass is not None and dpass.is_contiguous() and tuple(dpass.shape) == tuple(x0.shape):
-            acc, dpass = dpass, None
-        dx0, _ = _conv_backward_data(dy, weight, g, x0.shape[:3], x0.shape[3], 0, ihwo, acc, None, am_dy,
-                                     _amax_new(dy) if (want_dx_amax and am_dy is not None and dpass is None) else None)
-        if dpass is not None:
-            dx0 = dx0 + dpass
-    elif dpass is not None:
-        dx0 = dpass
+        acc0 = acc1 = None
+        if g.groups == 1 and _addable(dpass0, x0.shape, dy.dtype):
+            acc0, dpass0 = dpass0, None
+        if g.groups == 1 and x1 is not None and _addable(dpass1, x1.shape, dy.dtype):
+            acc1, dpass1 = dpass1, None
+        tok = _amax_new(dy) if (want_dx_amax and am_dy is not None and dpass0 is None) else None
+        dx0, dx1 = _conv_backward_data(dy, weight, g, x0.shape[:3], x0.shape[3], x1.shape[3] if x1 is not None else 0, ihwo,
+                                       acc0, acc1, am_dy, tok)
+        if dpass0 is not None:
+            dx0 = dx0 + dpass0
+        if dpass1 is not None:
+            dx1 = dx1 + dpass1
     dw = None
-    if need_dw:
-        wam = (_tok_ptr(am_x0), None, am_dy) if am_dy is not None else None
-        dw = _conv_backward_weight(x0, None, dy, weight, g, wparam, wam)
-    return dx0, dw
+    if need_dw:      # (after the input gradient: the weight-gradient launches go to the side stream)
+        dw = _conv_backward_weight(x0, x1, dy, weight, g, wparam, _amax_ptrs(am_in, am_dy) if am_dy is not None else None)
+    return dx0, dx1, dw
 
 
 class ConvFn(torch.autograd.Function):
@@ -1599,12 +1589,10 @@ class ConvFn(torch.autograd.Function):
     def backward(ctx, dy):
         x0, x1, weight = ctx.saved_tensors
         dy = _same(dy, x0 if x0.shape[-1] != 4 else dy).contiguous()
-        g = ctx.g
-        dx0 = dx1 = None
-        if ctx.needs_input_grad[0] or (x1 is not None and ctx.needs_input_grad[1]):
-            dx0, dx1 = _conv_backward_data(dy, weight, g, x0.shape[:3], x0.shape[3],
-                                           x1.shape[3] if x1 is not None else 0, None, None)
-        dw = _conv_backward_weight(x0, x1, dy, weight, g, ctx.wparam) if ctx.needs_input_grad[2] else None
+        need = ctx.needs_input_grad
+        # (no maxima: the node records none in forward and tells its kernels none)
+        dx0, dx1, dw = _conv_grads(x0, x1, weight, ctx.g, dy, None, None, None, None, False,
+                                   need[0] or (x1 is not None and need[1]), need[2], ctx.wparam)
         ctx.wparam = None
         db = None
         if ctx.has_bias and ctx.needs_input_grad[3]:
@@ -1745,10 +1733,8 @@ class BnActFn(torch.autograd.Function):
 
 
 def _acc_target(dpass, like_shape, like):
-    """the pass-through alias's gradient if the kernel can add onto it in place (same layout and element type), else None"""
-    if dpass is not None and dpass.is_contiguous() and tuple(dpass.shape) == tuple(like_shape) and dpass.dtype == like.dtype:
-        return dpass
-    return None
+    """the pass-through alias's gradient if the kernel can add onto it in place (_addable), else None"""
+    return dpass if _addable(dpass, like_shape, like.dtype) else None
 
 
 class MaxPool3x3s2Fn(torch.autograd.Function):
@@ -1916,8 +1902,8 @@ class SplitAttentionFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w1, b1, g1, be1, w2, b2, bn1, training):
         _need_cuda(x)
-        gap_part = getattr(x, "_xv2_gap_part", None)
-        if gap_part is not None:
+        claim = getattr(x, "_xv2_gap_part", None)      # (buffer, stamp) left by the producer's apply pass - _conv_bn_act_train
+        if claim is not None:
             x._xv2_gap_part = None          # one consumer, one use
         x = x.contiguous()
         N, H, W, C2 = x.shape
@@ -1940,9 +1926,10 @@ class SplitAttentionFn(torch.autograd.Function):
             out = _act((N, H, W, C), x)
             if training:
                 bn_stats_changed()
-            ws = _persist("splat", query("xv2_splat_gap_workspace", N, hw, C) // 4 + 16, x.device)
-            # (the producer's apply pass already took the pool's column sums - _conv_bn_act_train; the scratch is still the one it wrote)
-            gap_ready = 1 if (gap_part is not None and gap_part.data_ptr() == ws.data_ptr()) else 0
+            ws, stamp = _splat_scratch(N, hw, C, x.device)
+            # the producer's column sums are believed only while its launch is the LAST one handed this very buffer; after
+            # anything else (another block's tail, a backward, a regrown buffer) the tail takes the sums again
+            gap_ready = 1 if (claim is not None and claim[0] is ws and claim[1] == stamp - 1) else 0
             call("xv2_splat_tail_forward", x, N, hw, C, inter, w1m, b1, bn1.weight, bn1.bias, float(bn1.eps),
                  float(bn1.momentum), bn1.running_mean, bn1.running_var, 1 if training else 0, S, w2m, b2, gap, h1, a1,
                  mean1, invstd1, scale1, shift1, logits, att, out, ws, gap_ready, _dt(x))
@@ -1991,7 +1978,7 @@ class SplitAttentionFn(torch.autograd.Function):
             dx = torch.empty_like(x)
             call("xv2_splat_tail_backward", x, dout, N, hw, C, inter, gap, h1, a1, mean1, invstd1, g1, w1m, w2m, att,
                  1 if ctx.training else 0, ctx.split, datt, dlogits, da1, dh1, dgap, dw2, db2, dg1, dbe1, dw1, db1, dx,
-                 _persist("splat", query("xv2_splat_gap_workspace", N, hw, C) // 4 + 16, x.device), _dt(x))
+                 _splat_scratch(N, hw, C, x.device)[0], _dt(x))
             s1, s2 = ctx.shapes
             return dx, dw1.reshape(s1), (db1 if pb1 is not None else None), dg1, dbe1, dw2.reshape(s2), \
                 (db2 if pb2 is not None else None), None, None
