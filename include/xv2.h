@@ -610,6 +610,51 @@ int xv2_lovasz_forward(const float* logits, const uint8_t* labels, int N, int C,
 int xv2_lovasz_backward(const float* logits, int N, int C, int H, int W, const uint32_t* keys,
                         const uint32_t* sorted, const int* records, const double* sums,
                         const float* gscale, float* dlogits, void* stream);
+/* ---- "wce": cross-entropy with a per-pixel weight, class weights + border map (wce.hip, wce_px.h) ------------------------
+ * fp32 NCHW logits (C = 2 or 4), uint8 labels [N][LH][LW] sampled with `lstride` exactly as xv2_loss_forward samples them.
+ * post == 0: a pixel's class is its label.  post != 0: pixels with label 0 are dropped, the class is label - 1 (as
+ * XV2_LOSS_CE).  A pixel whose class is >= C is dropped as well.  With l(p) = logsumexp(x_p) - x_p[class] and
+ * w(p) = class_w[class(p)] + b(p) over the pixels that are not dropped:
+ *   loss    = sum_p w(p) l(p) / sum_p w(p)
+ *   dlogits = gscale[0] * w(p) * (softmax - onehot) / sum_p w(p)
+ * With b == 0 this is torch.nn.functional.cross_entropy(weight = class_w, reduction = "mean").  The weight is a constant of the
+ * labels: it gets no gradient.  sum w == 0 (no pixel left, or every present class weighted 0): loss is exactly +0 and dlogits
+ * exact zeros.  A NaN logit gives a NaN loss and the call returns.  class_w: C floats ON THE DEVICE, finite and >= 0 (the
+ * caller's duty: nothing is read back).  Sums are fp32 inside a thread and fp64 across threads in a fixed order: two calls give
+ * the same bits.  sums[2]: sum w l, sum w, owned by the caller until the backward call has run.  2 launches forward, 1 backward.
+ *
+ * Border term b(p), post == 0 only (Ronneberger et al., U-Net, 2015: w0 exp(-(d1 + d2)^2 / (2 sigma^2))).  Components are the
+ * 4-connected components of label > 0 in the FULL-RESOLUTION label map, as xv2_label_components numbers them.  For a
+ * background pixel p and a component k, delta_k(p) is the smallest squared pixel-centre distance dy^2 + dx^2 <= R^2 from p to
+ * a pixel of k inside the image (no padding: a pixel outside the image is no building).  D1(p) is the smallest delta_k, D2(p)
+ * the second smallest over the components (they may be equal); 0xFFFF stands for "none within R", and building pixels hold
+ * 0xFFFF in both.  D1 and D2 are integers in 1..1024 that depend on no scan order.
+ *   b(p) = w0 * exp(-(sqrt(D1) + sqrt(D2))^2 / (2 sigma^2)) where D2 != 0xFFFF, else 0,
+ * evaluated in fp32 as w0 * expf(-(D1 + D2 + 2 sqrtf(D1 D2)) / (2 sigma sigma)), each operation rounded once (D1 + D2 and
+ * D1 D2 <= 2^20 are exact), by ONE device function (wce_px.h) that the map entry, the forward and the backward pass share:
+ * their weights hold identical bits, and the backward pass never reads a stored float.  With lstride > 1 the distances stay
+ * those of the full-resolution labels, read at (y lstride, x lstride) like the labels: the geometry is in full-resolution
+ * pixels for every deep-supervision head.  Labelled buildings that touch in the raster are ONE component with no border
+ * between them: the map weights gaps that exist in the label, up to 2R wide.
+ *
+ * xv2_border_distances: labels uint8 [B][H][W] -> d1, d2 uint16 [B][H][W].  xv2_label_components into the workspace (int32
+ * per pixel), then one block per 32 x 32 tile with its (32 + 2R)^2 labels in LDS; nothing is read back, the launches do not
+ * depend on the content.  1 <= R <= 32, H W < 2^30, B <= 65535.
+ * xv2_border_weights: the fp32 map b alone over n entries (tests, utils/border_map.py).  w0 >= 0, sigma > 0, both finite.
+ * xv2_wce_forward / backward: d1 and d2 both NULL = no border term (w0 and sigma are then ignored), else [N][LH][LW] as above;
+ * post != 0 with distance maps is XV2_EINVAL.  N <= 65535.                                                                  */
+size_t xv2_border_workspace(int B, int H, int W);
+int xv2_border_distances(const uint8_t* labels, int B, int H, int W, int R, void* workspace, uint16_t* d1,
+                         uint16_t* d2, void* stream);
+int xv2_border_weights(const uint16_t* d1, const uint16_t* d2, int64_t n, float w0, float sigma, float* out,
+                       void* stream);
+size_t xv2_wce_workspace(int N, int C, int H, int W);
+int xv2_wce_forward(const float* logits, const uint8_t* labels, int N, int C, int H, int W, int lstride,
+                    int post, const float* class_w, const uint16_t* d1, const uint16_t* d2, float w0,
+                    float sigma, double* sums, float* loss, void* workspace, void* stream);
+int xv2_wce_backward(const float* logits, const uint8_t* labels, int N, int C, int H, int W, int lstride,
+                     int post, const float* class_w, const uint16_t* d1, const uint16_t* d2, float w0,
+                     float sigma, const double* sums, const float* gscale, float* dlogits, void* stream);
 /* argmax over channels of NCHW logits (utils/f1.py:14,36), equal to torch.argmax: the first maximum wins, a NaN is the
  * maximum and the first NaN wins */
 int xv2_argmax_nchw(const float* logits, int N, int C, int64_t hw, int add, uint8_t* labels,

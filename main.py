@@ -75,6 +75,14 @@ _LAUNCH_FLAGS = [
     # PL Trainer(accumulate_grad_batches): one optimizer step per K consecutive batches (not a flag of the reference's main.py)
     ("accumulate_grad_batches", dict(type=int, default=1,
                                      help="batches whose mean gradient takes one optimizer step (1: off)")),
+    # the weights of the wce loss term (criterion.Loss; not flags of the reference's main.py)
+    ("class_weights", dict(type=str, default=None,
+                           help="--loss_str wce: per-class weights w0,w1 (--type pre) or w0,w1,w2,w3 (--type post); none: all ones")),
+    ("border_weight", dict(type=float, default=0.0,
+                           help="--loss_str wce, --type pre: w0 of the border map w0 exp(-(d1 + d2)^2 / (2 sigma^2)) (0: off)")),
+    ("border_sigma", dict(type=float, default=5.0, help="sigma of the border map, in full-resolution pixels")),
+    ("border_radius", dict(type=int, default=0,
+                           help="search radius of the border map's distances, 1..32 pixels (0: min(32, ceil(3 sigma)))")),
     # synthetic-data knobs (not in the reference)
     ("train_size", dict(type=int, default=512)),
     ("eval_size", dict(type=int, default=1024)),

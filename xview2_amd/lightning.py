@@ -58,9 +58,10 @@ _VALUED = [
     ("dmg_model", dict(type=str, default="siamese", choices=DAMAGE_MODELS, help="network family of the damage task")),
     ("encoder", dict(type=str, default="resnest200", choices=ENCODERS, help="backbone of the U-Net")),
     ("loss_str", dict(type=str, default="focal+dice",
-                      help="'+'-joined terms out of dice, focal, ce, ohem, ohem_hard, lovasz, mse, coral (ohem is the reference's: "
-                           "mean CE; ohem_hard keeps all positives and the hardest quarter of each image's negatives; lovasz is "
-                           "the Lovasz-softmax surrogate of the Jaccard index)")),
+                      help="'+'-joined terms out of dice, focal, ce, ohem, ohem_hard, lovasz, wce, mse, coral (ohem is the "
+                           "reference's: mean CE; ohem_hard keeps all positives and the hardest quarter of each image's "
+                           "negatives; lovasz is the Lovasz-softmax surrogate of the Jaccard index; wce is cross-entropy weighted "
+                           "per pixel by --class_weights and the --border_weight map)")),
     ("warmup", dict(type=int, default=1, help="Noam schedule: epochs of linear warm-up")),
     ("init_lr", dict(type=float, default=1e-4, help="Noam schedule: rate at step 0")),
     ("final_lr", dict(type=float, default=1e-4, help="Noam schedule: rate at the last step")),

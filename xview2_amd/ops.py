@@ -2153,6 +2153,96 @@ class LovaszFn(torch.autograd.Function):
         return d, None, None, None
 
 
+BORDER_NONE = 0xFFFF      # "no component within R" in the maps of border_distances
+
+
+def _u8_labels(what, labels):
+    _need_cuda(labels)
+    if labels.dim() != 3:
+        raise ValueError("%s: labels must be [B,H,W], got %s" % (what, tuple(labels.shape)))
+    labels = labels.contiguous()
+    return labels if labels.dtype == torch.uint8 else labels.to(torch.uint8)
+
+
+def border_distances(labels, R):
+    """xv2_border_distances: labels [B,H,W] (label > 0 is a building) -> (d1, d2) uint16 [B,H,W], the squared distances from a
+    background pixel to the nearest and the second-nearest 4-connected component within R; BORDER_NONE where there is none
+    and on building pixels"""
+    labels = _u8_labels("border_distances", labels)
+    B, H, W = labels.shape
+    d1 = torch.empty((B, H, W), dtype=torch.uint16, device=labels.device)
+    d2 = torch.empty_like(d1)
+    ws = _ws(query("xv2_border_workspace", B, H, W), labels)
+    call("xv2_border_distances", labels, B, H, W, int(R), ws, d1, d2)
+    return d1, d2
+
+
+def border_weights(d1, d2, w0, sigma):
+    """xv2_border_weights: the fp32 map w0 exp(-(sqrt(d1) + sqrt(d2))^2 / (2 sigma^2)) of two maps of border_distances, 0 where
+    d2 is BORDER_NONE; the same device function as inside the loss"""
+    _need_cuda(d1)
+    if d1.dtype != torch.uint16 or d2.dtype != torch.uint16 or d1.shape != d2.shape:
+        raise ValueError("border_weights: d1 and d2 must be uint16 tensors of one shape")
+    d1, d2 = d1.contiguous(), d2.contiguous()
+    out = _f32(tuple(d1.shape), d1)
+    call("xv2_border_weights", d1, d2, d1.numel(), float(w0), float(sigma), out)
+    return out
+
+
+def _wce_border_args(border, labels):
+    if border is None:
+        return None, None, 0.0, 1.0
+    d1, d2, w0, sigma = border
+    if d1.dtype != torch.uint16 or d2.dtype != torch.uint16 or tuple(d1.shape) != tuple(labels.shape) or d2.shape != d1.shape \
+            or not (d1.is_contiguous() and d2.is_contiguous()):
+        raise ValueError("wce: d1 and d2 must be contiguous uint16 maps of the labels' shape %s" % (tuple(labels.shape),))
+    return d1, d2, float(w0), float(sigma)
+
+
+def wce_forward(logits, labels, class_w, lstride=1, post=False, border=None):
+    """xv2_wce_forward: (loss [1], sums [2] float64, logits, labels), the last two as handed to the kernels.  class_w: fp32 [C]
+    on the device.  border: None or (d1, d2, w0, sigma) with the maps of border_distances(labels, R)."""
+    _need_cuda(logits)
+    logits = logits.contiguous()
+    labels = _u8_labels("wce", labels)
+    N, C, H, W = logits.shape
+    if class_w.dtype != torch.float32 or class_w.numel() != C or class_w.device != logits.device:
+        raise ValueError("wce: class_w must hold %d fp32 weights on %s" % (C, logits.device))
+    class_w = class_w.contiguous()
+    d1, d2, w0, sigma = _wce_border_args(border, labels)
+    sums = torch.empty((2,), dtype=torch.float64, device=logits.device)
+    loss = _f32((1,), logits)
+    ws = _ws(query("xv2_wce_workspace", N, C, H, W), logits)
+    call("xv2_wce_forward", logits, labels, N, C, H, W, lstride, 1 if post else 0, class_w, d1, d2, w0, sigma, sums, loss, ws)
+    return loss, sums, logits, labels
+
+
+class WceFn(torch.autograd.Function):
+    """The ``wce`` term on NCHW logits (include/xv2.h, csrc/wce.hip): cross-entropy with the per-pixel weight
+    class_w[class] + border.  The sums belong to this node (deep supervision runs three forward passes before the first
+    backward); class_w and the distance maps d1 / d2 are read-only tensors that the heads of one batch share.  The backward
+    pass evaluates the weight again from the maps with the forward pass's own device function."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, class_w, lstride, post, d1, d2, w0, sigma):
+        border = None if d1 is None else (d1, d2, w0, sigma)
+        loss, sums, logits, labels = wce_forward(logits, labels, class_w, lstride, post, border)
+        ctx.save_for_backward(logits, labels, class_w, sums, *(() if d1 is None else (d1, d2)))
+        ctx.cfg = (lstride, post, float(w0), float(sigma))
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, gout):
+        logits, labels, class_w, sums = ctx.saved_tensors[:4]
+        d1, d2 = ctx.saved_tensors[4:] if len(ctx.saved_tensors) > 4 else (None, None)
+        lstride, post, w0, sigma = ctx.cfg
+        N, C, H, W = logits.shape
+        d = torch.empty_like(logits)
+        gs = gout.reshape(1).to(torch.float32).contiguous()
+        call("xv2_wce_backward", logits, labels, N, C, H, W, lstride, 1 if post else 0, class_w, d1, d2, w0, sigma, sums, gs, d)
+        return (d,) + (None,) * 8
+
+
 # ------------------------------------------------------------------------------------------------
 # Input hand-over on the device (SURVEY 8f row 4).  The reference's datasets normalise uint8 HWC tiles on the host and
 # transpose them to CHW (data_loading/pytorch_loader.py:63,90-91,145-147); the kernels here are NHWC, so a tile can go
