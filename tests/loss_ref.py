@@ -1,4 +1,4 @@
-"""Float64 restatement of the loss kernels (csrc/loss_optim.hip: loss_fwd_kernel, loss_finish_kernel, loss_bwd_kernel,
+"""Float64 restatement of the loss kernels (csrc/loss.hip: loss_fwd_kernel, loss_finish_kernel, loss_bwd_kernel,
 loss_aux_fwd_kernel, loss_aux_bwd_kernel; csrc/loss_px.h: softmax_px, label_at), the per-element error bounds they are
 held to, an fp32 transcription of the kernels' order of operations for the CPU test of those bounds, and the case tables
 that the CPU and the GPU test share.

@@ -1,4 +1,4 @@
-"""The loss, argmax and F1-count kernels (csrc/loss_optim.hip, csrc/loss_px.h) against the fp64 restatement and the derived
+"""The loss, argmax and F1-count kernels (csrc/loss.hip, csrc/loss_px.h) against the fp64 restatement and the derived
 per-element bounds of tests/loss_ref.py, on the case tables that tests/test_loss_ref_cpu.py checks without a GPU.
 
 The kernels are called through the C ABI.  Every output (dlogits, the 32 doubles of acc, the loss, the workspace of exactly
@@ -266,6 +266,14 @@ def test_argument_errors_come_before_any_launch():
     for terms, C in ((0, 2), (9, 4), (R.DICE, 3), (R.MSE, 2), (R.CORAL, 4), (7, 1)):
         with pytest.raises(RuntimeError):
             _capi.call("xv2_loss_forward", x, y, 1, C, 4, 6, 1, 0, terms, acc.view, loss.view, ws.view)
+    # lstride = 0, H = 0, N = 0 and a null labels pointer, forward and backward
+    d = Guarded(x.numel(), torch.float32, FILLS[1])
+    gs = torch.ones(1, dtype=torch.float32, device=dev())
+    for N, H, ls, labels in ((1, 4, 0, y), (1, 0, 1, y), (0, 4, 1, y), (1, 4, 1, None)):
+        with pytest.raises(RuntimeError):
+            _capi.call("xv2_loss_forward", x, labels, N, 4, H, 6, ls, 0, R.CE, acc.view, loss.view, ws.view)
+        with pytest.raises(RuntimeError):
+            _capi.call("xv2_loss_backward", x, labels, N, 4, H, 6, ls, 0, R.CE, acc.view, gs, 1.0, d.view)
     out = Guarded(24, torch.uint8, 7)
     with pytest.raises(RuntimeError):
         _capi.call("xv2_argmax_nchw", x, 1, 5, 24, 0, out.view)
@@ -276,7 +284,7 @@ def test_argument_errors_come_before_any_launch():
         with pytest.raises(RuntimeError):
             _capi.call("xv2_f1_counts", y, y, total, n_class, 0, counts.view)
     torch.cuda.synchronize()
-    for gd in (ws, acc, loss, out, counts):
+    for gd in (ws, acc, loss, d, out, counts):
         assert gd.intact(written=0)
 
 

@@ -246,6 +246,23 @@ def test_two_calls_are_bit_equal():
     assert np.array_equal(a[3], b[3]) and torch.equal(a[4], b[4])
 
 
+def test_backward_argument_errors_come_before_any_launch():
+    """lstride = 0, H = 0, N = 0 and a null labels pointer are refused on the host: dlogits and its guards keep their fill"""
+    from xview2_amd import _capi, ops
+    x, y = randn_case((1, 2, 4, 6), 0.3, 29)
+    loss, px, rec, sums, lg, lb = ops.ohem_forward(x.to(dev()), y.to(dev()))
+    gs = torch.ones(1, dtype=torch.float32, device=dev())
+    pad = 64
+    buf = torch.full((lg.numel() + 2 * pad,), 2.0 ** 100, dtype=torch.float32, device=dev())
+    before = buf.clone()
+    d = buf[pad:pad + lg.numel()]
+    for N, H, ls, labels in ((1, 4, 0, lb), (1, 0, 1, lb), (0, 4, 1, lb), (1, 4, 1, None)):
+        with pytest.raises(RuntimeError):
+            _capi.call("xv2_ohem_backward", lg, labels, N, 2, H, 6, ls, px, rec, sums, gs, d)
+    torch.cuda.synchronize()
+    assert torch.equal(buf, before)
+
+
 def _ds_inputs():
     g = torch.Generator().manual_seed(24)
     preds = [torch.randn(2, 2, s, s, generator=g) * 2 for s in (32, 16, 8)]

@@ -317,14 +317,6 @@ Plan plan(int H, int W, int R, int T) {
 
 }  // namespace
 
-#define AL_LAUNCH(kid, bytes, ...)                                  \
-    do {                                                            \
-        xv2::prof_begin(kid, 0.0, (double)(bytes), st);             \
-        hipLaunchKernelGGL(__VA_ARGS__);                            \
-        xv2::prof_end(st);                                          \
-        XV2_CHECK_LAUNCH();                                         \
-    } while (0)
-
 static int al_kid(int k) {
     static const int ids[] = {xv2::prof_register("al_sad_kernel"), xv2::prof_register("al_chunk_kernel"),
                               xv2::prof_register("al_total_kernel"), xv2::prof_register("al_translate_kernel")};
@@ -357,17 +349,17 @@ extern "C" int xv2_align_estimate(const uint8_t* pre, const uint8_t* post, int B
     const double px = (double)B * H * W;
     const dim3 grid(p.tiles, B), blk(256);
     if (T == 32)
-        AL_LAUNCH(al_kid(0), 6.0 * px, al_sad_kernel<32>, grid, blk, p.lds, st, pre, post, H, W, R, p.nbx, p.nb, p.psw, block_sad,
-                  block_shift);
+        XV2_LAUNCH(al_kid(0), 6.0 * px, al_sad_kernel<32>, grid, blk, p.lds, st, pre, post, H, W, R, p.nbx, p.nb, p.psw, block_sad,
+                   block_shift);
     else if (T == 64)
-        AL_LAUNCH(al_kid(0), 6.0 * px, al_sad_kernel<64>, grid, blk, p.lds, st, pre, post, H, W, R, p.nbx, p.nb, p.psw, block_sad,
-                  block_shift);
+        XV2_LAUNCH(al_kid(0), 6.0 * px, al_sad_kernel<64>, grid, blk, p.lds, st, pre, post, H, W, R, p.nbx, p.nb, p.psw, block_sad,
+                   block_shift);
     else
-        AL_LAUNCH(al_kid(0), 6.0 * px, al_sad_kernel<128>, grid, blk, p.lds, st, pre, post, H, W, R, p.nbx, p.nb, p.psw, block_sad,
-                  block_shift);
-    AL_LAUNCH(al_kid(1), 4.0 * B * p.tiles * p.DD, al_chunk_kernel, dim3((p.DD + 255) / 256, p.chunks, B), blk, 0, st,
-              block_sad, p.tiles, p.DD, chunk);
-    AL_LAUNCH(al_kid(2), 8.0 * B * p.chunks * p.DD, al_total_kernel, dim3(B), dim3(1024), 0, st, chunk, p.chunks, R, sad, shift);
+        XV2_LAUNCH(al_kid(0), 6.0 * px, al_sad_kernel<128>, grid, blk, p.lds, st, pre, post, H, W, R, p.nbx, p.nb, p.psw, block_sad,
+                   block_shift);
+    XV2_LAUNCH(al_kid(1), 4.0 * B * p.tiles * p.DD, al_chunk_kernel, dim3((p.DD + 255) / 256, p.chunks, B), blk, 0, st,
+               block_sad, p.tiles, p.DD, chunk);
+    XV2_LAUNCH(al_kid(2), 8.0 * B * p.chunks * p.DD, al_total_kernel, dim3(B), dim3(1024), 0, st, chunk, p.chunks, R, sad, shift);
     return XV2_OK;
 }
 
@@ -383,7 +375,7 @@ extern "C" int xv2_translate_u8(const uint8_t* src, int B, int H, int W, int C, 
     XV2_CHECK_ARG(s0 + n <= o0 || o0 + n <= s0, "translate_u8: out must not overlap src");
     hipStream_t st = (hipStream_t)stream;
     const int64_t hw = (int64_t)H * W;
-    AL_LAUNCH(al_kid(3), 2.0 * n, al_translate_kernel, dim3((unsigned)xv2::cdiv(hw, 256), B), dim3(256), 0, st, src, H, W, C,
-              shift, out);
+    XV2_LAUNCH(al_kid(3), 2.0 * n, al_translate_kernel, dim3((unsigned)xv2::cdiv(hw, 256), B), dim3(256), 0, st, src, H, W, C,
+               shift, out);
     return XV2_OK;
 }

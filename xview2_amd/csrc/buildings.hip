@@ -232,14 +232,6 @@ int64_t chunks_of(int H, int W) { return ((int64_t)H * W + CHUNK - 1) / CHUNK; }
 
 }  // namespace
 
-#define BT_LAUNCH(kid, bytes, ...)                                  \
-    do {                                                            \
-        xv2::prof_begin(kid, 0.0, (double)(bytes), st);             \
-        hipLaunchKernelGGL(__VA_ARGS__);                            \
-        xv2::prof_end(st);                                          \
-        XV2_CHECK_LAUNCH();                                         \
-    } while (0)
-
 static int bt_kid(int k) {
     static const int ids[] = {xv2::prof_register("bt_count_kernel"), xv2::prof_register("bt_scan_kernel"),
                               xv2::prof_register("bt_rank_kernel"), xv2::prof_register("bt_accum_kernel"),
@@ -272,13 +264,13 @@ extern "C" int xv2_building_table(const int32_t* labels, const uint8_t* dmg, con
     unsigned* chunk_cnt = reinterpret_cast<unsigned*>(ws + align256(4 * (size_t)B * hw));
     const int rx = (W + RW - 1) / RW, ry = (H + RH - 1) / RH;
     const double px = (double)B * hw;
-    BT_LAUNCH(bt_kid(0), px * 4, bt_count_kernel, dim3(nchunks, B), dim3(256), 0, st, labels, hw, nchunks, chunk_cnt);
-    BT_LAUNCH(bt_kid(1), 8.0 * B * nchunks, bt_scan_kernel, dim3(B), dim3(SCAN_T), 0, st, chunk_cnt, nchunks, count);
-    BT_LAUNCH(bt_kid(2), px * 4, bt_rank_kernel, dim3(nchunks, B), dim3(256), 0, st, labels, hw, nchunks, chunk_cnt,
-              max_rows, rank_map, rows);
-    BT_LAUNCH(bt_kid(3), px * (loc ? 9 : 5), bt_accum_kernel, dim3((unsigned)rx * ry, B), dim3(256), 0, st, labels, dmg, loc,
-              H, W, rx, max_rows, rank_map, rows);
-    BT_LAUNCH(bt_kid(4), 48.0 * B * max_rows, bt_finish_kernel, dim3((max_rows + 255) / 256, B), dim3(256), 0, st, rows, count,
-              max_rows);
+    XV2_LAUNCH(bt_kid(0), px * 4, bt_count_kernel, dim3(nchunks, B), dim3(256), 0, st, labels, hw, nchunks, chunk_cnt);
+    XV2_LAUNCH(bt_kid(1), 8.0 * B * nchunks, bt_scan_kernel, dim3(B), dim3(SCAN_T), 0, st, chunk_cnt, nchunks, count);
+    XV2_LAUNCH(bt_kid(2), px * 4, bt_rank_kernel, dim3(nchunks, B), dim3(256), 0, st, labels, hw, nchunks, chunk_cnt,
+               max_rows, rank_map, rows);
+    XV2_LAUNCH(bt_kid(3), px * (loc ? 9 : 5), bt_accum_kernel, dim3((unsigned)rx * ry, B), dim3(256), 0, st, labels, dmg, loc,
+               H, W, rx, max_rows, rank_map, rows);
+    XV2_LAUNCH(bt_kid(4), 48.0 * B * max_rows, bt_finish_kernel, dim3((max_rows + 255) / 256, B), dim3(256), 0, st, rows, count,
+               max_rows);
     return XV2_OK;
 }

@@ -42,12 +42,6 @@ constexpr int LOV_KEY_BLOCKS = 1024, LOV_SUM_BLOCKS = 2048;
 
 static inline int lov_blocks(int64_t total, int cap) { return (int)std::min<int64_t>(std::max<int64_t>(cdiv(total, LOV_CHUNK), 1), cap); }
 
-__device__ __forceinline__ int wave_sum_int(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // first index in [lo, hi) whose key is >= v (lower) / > v (upper); hi when there is none
 __device__ __forceinline__ int lov_lower(const unsigned* __restrict__ S, int lo, int hi, unsigned v) {
     while (lo < hi) {
@@ -118,11 +112,10 @@ __global__ void __launch_bounds__(256) lovasz_key_kernel(const float* __restrict
 #pragma unroll
     for (int c = 0; c <= C; ++c) g[c] = 0;
     for (int64_t i = i0 + threadIdx.x; i < i1; i += 256) {
-        const int64_t n = i / hw, q = i - n * hw;
-        const int h = (int)(q / W), w = (int)(q - (int64_t)h * W);
-        const int y = label_at(labels, n, h, w, H, W, ls);
+        const Px px = px_decode<C>(i, hw, W);
+        const int y = label_at(labels, px.n, px.h, px.w, H, W, ls);
         float p[C], lse;
-        softmax_px<C>(logits, n * C * hw + q, hw, p, lse);
+        softmax_px<C>(logits, px.base, hw, p, lse);
         const bool skip = post && y == 0;
         const int cls = post ? y - 1 : y;
         g[C] += skip ? 1 : 0;
@@ -140,15 +133,7 @@ __global__ void __launch_bounds__(256) lovasz_key_kernel(const float* __restrict
             keys[c * total + i] = key;
         }
     }
-#pragma unroll
-    for (int c = 0; c <= C; ++c) {
-        const int v = wave_sum_int(g[c]);
-        if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6][c] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x <= C)
-        cnt_part[(size_t)blockIdx.x * (C + 1) + threadIdx.x] =
-            sh[0][threadIdx.x] + sh[1][threadIdx.x] + sh[2][threadIdx.x] + sh[3][threadIdx.x];
+    block_sum_store(g, sh, cnt_part + (size_t)blockIdx.x * (C + 1));
 }
 
 // one block: the B partial counts in a fixed order -> records
@@ -159,7 +144,7 @@ __global__ void __launch_bounds__(256) lovasz_count_kernel(const int* __restrict
     for (int b = threadIdx.x; b < B; b += 256)
         for (int c = 0; c <= C; ++c) a[c] += cnt_part[(size_t)b * (C + 1) + c];
     for (int c = 0; c <= C; ++c) {
-        const int v = wave_sum_int(a[c]);
+        const int v = wave_sum(a[c]);
         if ((threadIdx.x & 63) == 0) sh[c][threadIdx.x >> 6] = v;
     }
     __syncthreads();
@@ -177,12 +162,12 @@ __global__ void __launch_bounds__(256) lovasz_count_kernel(const int* __restrict
 // a chunk are ascending, so what its first and its last entry find in the other segment bounds every search in between.
 __global__ void __launch_bounds__(256) lovasz_sum_kernel(const unsigned* __restrict__ sorted, int64_t total, int64_t chunk, int c0,
                                                          const int* __restrict__ rec, double* __restrict__ part) {
-    __shared__ double sh[4];
+    __shared__ double sh[4][1];
     __shared__ int rng[4];
     const int c = c0 + blockIdx.y;
     const int G = rec[c * LOV_REC], Nb = rec[c * LOV_REC + 1];
     const unsigned* S = sorted + (size_t)c * total;
-    double a = 0.0;
+    double a[1] = {0.0};
     if (rec[c * LOV_REC + 3]) {            // the same for the whole block
         const int64_t j0 = blockIdx.x * chunk, j1 = min(j0 + chunk, (int64_t)Nb + G);
         const int64_t b1 = min(j1, (int64_t)Nb), f0 = max(j0, (int64_t)Nb);
@@ -208,13 +193,10 @@ __global__ void __launch_bounds__(256) lovasz_sum_kernel(const unsigned* __restr
             } else {
                 w = lov_fg_weight(G, Nb, lov_upper(S, rng[2], rng[3], key & ~LOV_SIGN));
             }
-            a += (double)__uint_as_float(key & ~LOV_SIGN) * w;
+            a[0] += (double)__uint_as_float(key & ~LOV_SIGN) * w;
         }
     }
-    a = wave_sum(a);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = a;
-    __syncthreads();
-    if (threadIdx.x == 0) part[(size_t)c * gridDim.x + blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
+    block_sum_store(a, sh, part + (size_t)c * gridDim.x + blockIdx.x);
 }
 
 // one block: each class's partials, strided over the threads and then across them in a fixed order; the mean over present classes
@@ -222,19 +204,13 @@ __global__ void __launch_bounds__(256) lovasz_finish_kernel(const double* __rest
                                                             const int* __restrict__ rec, double* __restrict__ sums,
                                                             float* __restrict__ loss) {
     __shared__ double sh[4][4];
-    for (int c = 0; c < 4; ++c) {
-        double a = 0.0;
-        if (c < C && rec[c * LOV_REC + 3])
-            for (int b = threadIdx.x; b < B; b += 256) a += part[(size_t)c * B + b];
-        a = wave_sum(a);
-        if ((threadIdx.x & 63) == 0) sh[c][threadIdx.x >> 6] = a;
-    }
+    for (int c = 0; c < 4; ++c) strided_wave_total(part + (size_t)c * B, (c < C && rec[c * LOV_REC + 3]) ? B : 0, 1, sh[c]);
     __syncthreads();
     if (threadIdx.x != 0) return;
     double tot = 0.0;
     int np = 0;
     for (int k = 0; k < LOV_NPRESENT; ++k) {
-        const double lc = sh[k][0] + sh[k][1] + sh[k][2] + sh[k][3];
+        const double lc = wave4_total(sh[k]);
         sums[k] = lc;
         if (k < C && rec[k * LOV_REC + 3]) {
             tot += lc;
@@ -294,8 +270,7 @@ __global__ void __launch_bounds__(256) lovasz_bwd_kernel(const float* __restrict
             any = true;
         }
         if (!any) {
-#pragma unroll
-            for (int c = 0; c < C; ++c) dlogits[base + c * hw] = 0.f;
+            zero_px<C>(dlogits, base, hw);
             continue;
         }
         float p[C], lse;
@@ -308,14 +283,6 @@ __global__ void __launch_bounds__(256) lovasz_bwd_kernel(const float* __restrict
     }
 }
 
-#define LOV_LAUNCH(kid, bytes, ...)                     \
-    do {                                                \
-        prof_begin(lov_kid(kid), 0.0, (double)(bytes), st); \
-        hipLaunchKernelGGL(__VA_ARGS__);                \
-        prof_end(st);                                   \
-        XV2_CHECK_LAUNCH();                             \
-    } while (0)
-
 enum { K_KEY, K_COUNT, K_SUM, K_FINISH, K_BWD };
 static int lov_kid(int k) {
     static const int ids[] = {prof_register("lovasz_key_kernel"), prof_register("lovasz_count_kernel"),
@@ -324,9 +291,8 @@ static int lov_kid(int k) {
     return ids[k];
 }
 
-static int lov_check(int N, int C, int H, int W, int64_t& total) {
-    XV2_CHECK_ARG(C == 2 || C == 4, "lovasz: C=%d unsupported (2 or 4)", C);
-    XV2_CHECK_ARG(N >= 1 && H >= 1 && W >= 1, "lovasz: bad shape N=%d H=%d W=%d", N, H, W);
+static int lov_check(int N, int C, int H, int W, int lstride, int64_t& total) {
+    if (int rc = loss_check("lovasz", N, C, H, W, lstride)) return rc;
     total = (int64_t)N * H * W;
     XV2_CHECK_ARG(total < ((int64_t)1 << 30), "lovasz: N*H*W=%lld entries unsupported (< 2^30)", (long long)total);
     return XV2_OK;
@@ -357,46 +323,37 @@ extern "C" int xv2_lovasz_forward(const float* logits, const uint8_t* labels, in
                                   unsigned class_mask, uint32_t* keys, uint32_t* sorted, int* records, double* sums, float* loss,
                                   void* workspace, void* stream) {
     int64_t total = 0;
-    if (int rc = lov_check(N, C, H, W, total)) return rc;
-    XV2_CHECK_ARG(lstride >= 1, "lovasz: bad lstride=%d", lstride);
+    if (int rc = lov_check(N, C, H, W, lstride, total)) return rc;
     XV2_CHECK_ARG(class_mask != 0u && class_mask < (1u << C), "lovasz: class_mask=0x%x names no class or one beyond C=%d",
                   class_mask, C);
     hipStream_t st = (hipStream_t)stream;
     const LovWs ws = lov_ws(workspace, C);
     const int Bk = lov_blocks(total, LOV_KEY_BLOCKS), Bs = lov_blocks(total, LOV_SUM_BLOCKS);
     const double npx = (double)total;
-    if (C == 2)
-        LOV_LAUNCH(K_KEY, npx * (8 * C + 1), lovasz_key_kernel<2>, dim3(Bk), dim3(256), 0, st, logits, labels, N, H, W, lstride,
-                   post, cdiv(total, Bk), keys, ws.cnt);
-    else
-        LOV_LAUNCH(K_KEY, npx * (8 * C + 1), lovasz_key_kernel<4>, dim3(Bk), dim3(256), 0, st, logits, labels, N, H, W, lstride,
-                   post, cdiv(total, Bk), keys, ws.cnt);
-    LOV_LAUNCH(K_COUNT, 4.0 * Bk * (C + 1), lovasz_count_kernel, dim3(1), dim3(256), 0, st, ws.cnt, Bk, C, total, class_mask,
+    XV2_DISPATCH_C24(C, XV2_LAUNCH(lov_kid(K_KEY), npx * (8 * C + 1), lovasz_key_kernel<CC>, dim3(Bk), dim3(256), 0, st, logits, labels,
+                                   N, H, W, lstride, post, cdiv(total, Bk), keys, ws.cnt));
+    XV2_LAUNCH(lov_kid(K_COUNT), 4.0 * Bk * (C + 1), lovasz_count_kernel, dim3(1), dim3(256), 0, st, ws.cnt, Bk, C, total, class_mask,
                records);
     int c0, c1;
     lov_span(class_mask, c0, c1);
     const int R = c1 - c0 + 1;
     if (int rc = xv2_sort_u32(keys + (size_t)c0 * total, sorted + (size_t)c0 * total, R, total, ws.sort, stream)) return rc;
-    LOV_LAUNCH(K_SUM, npx * R * 4, lovasz_sum_kernel, dim3(Bs, R), dim3(256), 0, st, sorted, total, cdiv(total, Bs), c0, records,
+    XV2_LAUNCH(lov_kid(K_SUM), npx * R * 4, lovasz_sum_kernel, dim3(Bs, R), dim3(256), 0, st, sorted, total, cdiv(total, Bs), c0, records,
                ws.part);
-    LOV_LAUNCH(K_FINISH, 8.0 * Bs * R, lovasz_finish_kernel, dim3(1), dim3(256), 0, st, ws.part, Bs, C, records, sums, loss);
+    XV2_LAUNCH(lov_kid(K_FINISH), 8.0 * Bs * R, lovasz_finish_kernel, dim3(1), dim3(256), 0, st, ws.part, Bs, C, records, sums, loss);
     return XV2_OK;
 }
 
 extern "C" int xv2_lovasz_backward(const float* logits, int N, int C, int H, int W, const uint32_t* keys, const uint32_t* sorted,
                                    const int* records, const double* sums, const float* gscale, float* dlogits, void* stream) {
     int64_t total = 0;
-    if (int rc = lov_check(N, C, H, W, total)) return rc;
+    if (int rc = lov_check(N, C, H, W, 1, total)) return rc;      // (the backward pass reads no label)
     hipStream_t st = (hipStream_t)stream;
     const int64_t hw = (int64_t)H * W;
     // 8 pixels per thread and more on large inputs: a block fills its sample tables once
     const int grid = (int)std::min<int64_t>(cdiv(total, 2048), 2048);
     const double bytes = (double)total * (8 * C + 4 * C);
-    if (C == 2)
-        LOV_LAUNCH(K_BWD, bytes, lovasz_bwd_kernel<2>, dim3(grid), dim3(256), 0, st, logits, hw, total, keys, sorted, records,
-                   sums, gscale, dlogits);
-    else
-        LOV_LAUNCH(K_BWD, bytes, lovasz_bwd_kernel<4>, dim3(grid), dim3(256), 0, st, logits, hw, total, keys, sorted, records,
-                   sums, gscale, dlogits);
+    XV2_DISPATCH_C24(C, XV2_LAUNCH(lov_kid(K_BWD), bytes, lovasz_bwd_kernel<CC>, dim3(grid), dim3(256), 0, st, logits, hw, total, keys,
+                                   sorted, records, sums, gscale, dlogits));
     return XV2_OK;
 }

@@ -263,14 +263,6 @@ int log2_slots(int cap) {
 
 }  // namespace
 
-#define MT_LAUNCH(kid, bytes, ...)                                  \
-    do {                                                            \
-        xv2::prof_begin(kid, 0.0, (double)(bytes), st);             \
-        hipLaunchKernelGGL(__VA_ARGS__);                            \
-        xv2::prof_end(st);                                          \
-        XV2_CHECK_LAUNCH();                                         \
-    } while (0)
-
 static int mt_kid(int k) {
     static const int ids[] = {xv2::prof_register("mt_overlap_kernel"), xv2::prof_register("mt_init_kernel"),
                               xv2::prof_register("mt_insert_kernel"),  xv2::prof_register("mt_offer_kernel"),
@@ -321,7 +313,7 @@ extern "C" int xv2_building_match(const int32_t* labels_p, const int64_t* rows_p
     u64* sums = reinterpret_cast<u64*>(ws + align256(8 * (size_t)B * slots));
 
     const dim3 blk(256), per_pixel((unsigned)xv2::cdiv(hw, 256), B), per_slot((unsigned)xv2::cdiv(slots, 256), B);
-    MT_LAUNCH(mt_kid(0), 9.0 * n, mt_overlap_kernel, per_pixel, blk, 0, st, labels_p, labels_t, hw, mask);
+    XV2_LAUNCH(mt_kid(0), 9.0 * n, mt_overlap_kernel, per_pixel, blk, 0, st, labels_p, labels_t, hw, mask);
     if (int rc = xv2_label_components(mask, B, H, W, nullptr, plabels, stream)) return rc;
     // the mask doubles as the damage map (every piece pixel is class 1); only columns 0 and 1 of a piece's row are used
     if (int rc = xv2_building_table(plabels, mask, nullptr, B, H, W, cap, table_ws, pieces, piece_count, stream)) return rc;
@@ -331,16 +323,16 @@ extern "C" int xv2_building_match(const int32_t* labels_p, const int64_t* rows_p
     const dim3 per_row((unsigned)row_blocks, B, 2);
     const dim3 init((unsigned)(row_blocks > slot_blocks ? row_blocks : slot_blocks), B, 3);
     const double row_bytes = 64.0 * B * ((double)max_rows_p + max_rows_t);
-    MT_LAUNCH(mt_kid(1), row_bytes + 16.0 * B * slots, mt_init_kernel, init, blk, 0, st, count_p, max_rows_p, match_p, count_t,
-              max_rows_t, match_t, keys, sums, slots);
-    MT_LAUNCH(mt_kid(2), 64.0 * B * cap, mt_insert_kernel, dim3((cap + 255) / 256, B), blk, 0, st, labels_p, rows_p, count_p,
-              max_rows_p, labels_t, rows_t, count_t, max_rows_t, hw, pieces, piece_count, cap, log2s, keys, sums, match_p,
-              match_t);
-    MT_LAUNCH(mt_kid(3), 16.0 * B * slots, mt_offer_kernel, per_slot, blk, 0, st, rows_p, max_rows_p, rows_t, max_rows_t,
-              log2s, keys, sums, match_p, match_t);
-    MT_LAUNCH(mt_kid(4), row_bytes, mt_resolve_kernel, per_row, blk, 0, st, rows_p, count_p, max_rows_p, rows_t, count_t,
-              max_rows_t, iou_num, iou_den, match_p, match_t);
-    MT_LAUNCH(mt_kid(5), row_bytes / 8, mt_tidy_kernel, per_row, blk, 0, st, count_p, max_rows_p, match_p, count_t, max_rows_t,
-              match_t);
+    XV2_LAUNCH(mt_kid(1), row_bytes + 16.0 * B * slots, mt_init_kernel, init, blk, 0, st, count_p, max_rows_p, match_p, count_t,
+               max_rows_t, match_t, keys, sums, slots);
+    XV2_LAUNCH(mt_kid(2), 64.0 * B * cap, mt_insert_kernel, dim3((cap + 255) / 256, B), blk, 0, st, labels_p, rows_p, count_p,
+               max_rows_p, labels_t, rows_t, count_t, max_rows_t, hw, pieces, piece_count, cap, log2s, keys, sums, match_p,
+               match_t);
+    XV2_LAUNCH(mt_kid(3), 16.0 * B * slots, mt_offer_kernel, per_slot, blk, 0, st, rows_p, max_rows_p, rows_t, max_rows_t,
+               log2s, keys, sums, match_p, match_t);
+    XV2_LAUNCH(mt_kid(4), row_bytes, mt_resolve_kernel, per_row, blk, 0, st, rows_p, count_p, max_rows_p, rows_t, count_t,
+               max_rows_t, iou_num, iou_den, match_p, match_t);
+    XV2_LAUNCH(mt_kid(5), row_bytes / 8, mt_tidy_kernel, per_row, blk, 0, st, count_p, max_rows_p, match_p, count_t, max_rows_t,
+               match_t);
     return XV2_OK;
 }

@@ -1,6 +1,6 @@
 // "ohem_hard": online hard example mining (arXiv 1812.05802) as model/loss.py:24-51 reads once the k hardest negatives
 // are really selected (the reference slices the (values, indices) tuple of sort, so its "ohem" keeps every negative;
-// that stays XV2_LOSS_CE in loss_optim.hip).
+// that stays XV2_LOSS_CE in loss.hip).
 //
 // Per image i, with l = logsumexp(x) - x[y] per pixel: positives (y > 0) are all kept, of the Cn negatives (y == 0)
 // the k = min(Cn, max(Cn / 4, 5, 2 Cp)) with the largest l.  loss = sum_i (sum l over positives + sum of the k largest
@@ -54,24 +54,18 @@ static inline OhemWs ohem_ws(void* ws, int N, int B) {
     return o;
 }
 
-__device__ __forceinline__ void block_sum_store(float a, double* sh4, double* dst) {
-    const double v = wave_sum((double)a);
-    if ((threadIdx.x & 63) == 0) sh4[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) *dst = sh4[0] + sh4[1] + sh4[2] + sh4[3];
-}
-
 // grid (B, N): block b owns pixels [b * chunk, (b + 1) * chunk) of image n
 template <int C>
 __global__ void __launch_bounds__(256) ohem_px_kernel(const float* __restrict__ logits, const uint8_t* __restrict__ labels,
                                                        int H, int W, int ls, int64_t chunk, float* __restrict__ px_loss,
                                                        double* __restrict__ pos_part) {
-    __shared__ double sh[4];
+    __shared__ double sh[4][1];
     const int64_t hw = (int64_t)H * W, n = blockIdx.y;
     const int64_t q0 = blockIdx.x * chunk, q1 = min(q0 + chunk, hw);
-    float a = 0.f;
+    float a[1] = {0.f};
     for (int64_t q = q0 + threadIdx.x; q < q1; q += 256) {
-        const int h = (int)(q / W), w = (int)(q - (int64_t)h * W);
+        int h, w;
+        px_hw(q, W, h, w);
         const int y = label_at(labels, n, h, w, H, W, ls);
         const int64_t base = n * C * hw + q;
         float x[C], m = -INFINITY;
@@ -83,6 +77,8 @@ __global__ void __launch_bounds__(256) ohem_px_kernel(const float* __restrict__ 
         float s = 0.f;
 #pragma unroll
         for (int c = 0; c < C; ++c) s += expf(x[c] - m);
+        // pick<C>(x, y), spelled out: handed to a function by reference, x[4] is kept in LDS and x[y] read back from there
+        // (4 KB per block and a round trip per pixel at C = 4); this chain stays in registers
         float xy = x[0];
 #pragma unroll
         for (int c = 1; c < C; ++c) xy = (y == c) ? x[c] : xy;
@@ -91,7 +87,7 @@ __global__ void __launch_bounds__(256) ohem_px_kernel(const float* __restrict__ 
         // canonical form for the select: NaN is ONE pattern above +Inf, zero is +0 (never -0, never below zero)
         if (!(l > 0.f)) l = (l != l) ? __uint_as_float(OHEM_NAN) : 0.f;
         if (y > 0) {
-            a += l;
+            a[0] += l;
             l = -1.f;
         }
         px_loss[n * hw + q] = l;
@@ -219,21 +215,22 @@ __global__ void __launch_bounds__(1024) ohem_scan_kernel(const int* __restrict__
 // grid (B, N): fp64 partial sum of the image's candidates above its threshold
 __global__ void __launch_bounds__(256) ohem_sum_kernel(const unsigned* __restrict__ vals, int64_t M, int64_t chunk,
                                                         const int* __restrict__ rec, double* __restrict__ neg_part) {
-    __shared__ double sh[4];
+    __shared__ double sh[4][1];
     const int64_t n = blockIdx.y;
     const int k = rec[n * OHEM_REC + 2];
     const unsigned tb = (unsigned)rec[n * OHEM_REC + 3];
     const int64_t q0 = blockIdx.x * chunk, q1 = min(q0 + chunk, M);
-    float a = 0.f;
+    float a[1] = {0.f};
     if (k > 0)
         for (int64_t q = q0 + threadIdx.x; q < q1; q += 256) {
             unsigned key;
-            if (ohem_key(vals[n * M + q], key) && key > tb) a += __uint_as_float(key);
+            if (ohem_key(vals[n * M + q], key) && key > tb) a[0] += __uint_as_float(key);
         }
     block_sum_store(a, sh, neg_part + (size_t)n * gridDim.x + blockIdx.x);
 }
 
-// one block: the partials in a fixed order, r * t per image, the loss; sums = {positive sum, selected-negative sum, samples}
+// one block: the partials strided over the threads, then 256 serial terms (this order is part of the result), r * t per image,
+// the loss; sums = {positive sum, selected-negative sum, samples}
 __global__ void __launch_bounds__(256) ohem_finish_kernel(const double* __restrict__ pos_part,
                                                            const double* __restrict__ neg_part, int nparts, int N,
                                                            const int* __restrict__ rec, double* __restrict__ sums,
@@ -274,14 +271,13 @@ __global__ void __launch_bounds__(256) ohem_bwd_kernel(const float* __restrict__
     const int64_t hw = (int64_t)H * W, total = (int64_t)N * hw;
     const float gs = gscale[0] * (float)(1.0 / sums[2]);
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t n = i / hw, q = i - n * hw;
-        const int64_t base = n * C * hw + q;
+        const Px px = px_decode<C>(i, hw, W);
+        const int64_t n = px.n, base = px.base;
         unsigned key;
         int y = 0;
         float wgt;
         if (!ohem_key(px_loss[i], key)) {          // a positive: always kept
-            const int h = (int)(q / W), w = (int)(q - (int64_t)h * W);
-            y = label_at(labels, n, h, w, H, W, ls);
+            y = label_at(labels, n, px.h, px.w, H, W, ls);
             wgt = 1.f;
         } else {
             const int* r = rec + n * OHEM_REC;
@@ -289,8 +285,7 @@ __global__ void __launch_bounds__(256) ohem_bwd_kernel(const float* __restrict__
             wgt = (r[2] == 0 || key < tb) ? 0.f : (key > tb ? 1.f : (float)r[6] / (float)r[5]);
         }
         if (wgt == 0.f) {
-#pragma unroll
-            for (int c = 0; c < C; ++c) dlogits[base + c * hw] = 0.f;
+            zero_px<C>(dlogits, base, hw);
             continue;
         }
         float p[C], lse;
@@ -300,15 +295,6 @@ __global__ void __launch_bounds__(256) ohem_bwd_kernel(const float* __restrict__
         for (int c = 0; c < C; ++c) dlogits[base + c * hw] = s * (p[c] - ((y == c) ? 1.f : 0.f));
     }
 }
-
-// every launch is bracketed for the bench-time profiler (xv2_prof_enable; no-ops otherwise); bytes: algorithmic traffic
-#define OHEM_LAUNCH(kid, bytes, ...)                    \
-    do {                                                \
-        prof_begin(ohem_kid(kid), 0.0, (double)(bytes), st); \
-        hipLaunchKernelGGL(__VA_ARGS__);                \
-        prof_end(st);                                   \
-        XV2_CHECK_LAUNCH();                             \
-    } while (0)
 
 enum { K_PX, K_HIST, K_SCAN, K_SUM, K_FINISH, K_BWD };
 static int ohem_kid(int k) {
@@ -322,12 +308,12 @@ static int ohem_select(const unsigned* vals, int N, int64_t M, const int* kin, i
     const int64_t chunk = cdiv(M, B);
     const dim3 grid(B, N);
     const double tbl = (double)N * B * OHEM_BINS * sizeof(int);
-    OHEM_LAUNCH(K_HIST, 4.0 * N * M + tbl, ohem_hist_kernel<0>, grid, dim3(256), 0, st, vals, M, chunk, rec, ws.tables);
-    OHEM_LAUNCH(K_SCAN, tbl, ohem_scan_kernel, dim3(N), dim3(1024), 0, st, ws.tables, B, M, kin, 0, rec);
-    OHEM_LAUNCH(K_HIST, 4.0 * N * M + tbl, ohem_hist_kernel<1>, grid, dim3(256), 0, st, vals, M, chunk, rec, ws.tables);
-    OHEM_LAUNCH(K_SCAN, tbl, ohem_scan_kernel, dim3(N), dim3(1024), 0, st, ws.tables, B, M, kin, 1, rec);
-    OHEM_LAUNCH(K_HIST, 4.0 * N * M + tbl, ohem_hist_kernel<2>, grid, dim3(256), 0, st, vals, M, chunk, rec, ws.tables);
-    OHEM_LAUNCH(K_SCAN, tbl, ohem_scan_kernel, dim3(N), dim3(1024), 0, st, ws.tables, B, M, kin, 2, rec);
+    XV2_LAUNCH(ohem_kid(K_HIST), 4.0 * N * M + tbl, ohem_hist_kernel<0>, grid, dim3(256), 0, st, vals, M, chunk, rec, ws.tables);
+    XV2_LAUNCH(ohem_kid(K_SCAN), tbl, ohem_scan_kernel, dim3(N), dim3(1024), 0, st, ws.tables, B, M, kin, 0, rec);
+    XV2_LAUNCH(ohem_kid(K_HIST), 4.0 * N * M + tbl, ohem_hist_kernel<1>, grid, dim3(256), 0, st, vals, M, chunk, rec, ws.tables);
+    XV2_LAUNCH(ohem_kid(K_SCAN), tbl, ohem_scan_kernel, dim3(N), dim3(1024), 0, st, ws.tables, B, M, kin, 1, rec);
+    XV2_LAUNCH(ohem_kid(K_HIST), 4.0 * N * M + tbl, ohem_hist_kernel<2>, grid, dim3(256), 0, st, vals, M, chunk, rec, ws.tables);
+    XV2_LAUNCH(ohem_kid(K_SCAN), tbl, ohem_scan_kernel, dim3(N), dim3(1024), 0, st, ws.tables, B, M, kin, 2, rec);
     return XV2_OK;
 }
 
@@ -358,8 +344,7 @@ extern "C" int xv2_topk_select(const float* values, int N, int64_t M, const int*
 
 extern "C" int xv2_ohem_forward(const float* logits, const uint8_t* labels, int N, int C, int H, int W, int lstride,
                                 float* px_loss, int* records, double* sums, float* loss, void* workspace, void* stream) {
-    XV2_CHECK_ARG(C == 2 || C == 4, "ohem: C=%d unsupported (2 or 4)", C);
-    XV2_CHECK_ARG(H >= 1 && W >= 1 && lstride >= 1, "ohem: bad shape H=%d W=%d lstride=%d", H, W, lstride);
+    if (int rc = loss_check("ohem", N, C, H, W, lstride)) return rc;
     const int64_t M = (int64_t)H * W;
     if (int rc = ohem_check_shape(N, M)) return rc;
     hipStream_t st = (hipStream_t)stream;
@@ -368,24 +353,21 @@ extern "C" int xv2_ohem_forward(const float* logits, const uint8_t* labels, int 
     const OhemWs ws = ohem_ws(workspace, N, B);
     const dim3 grid(B, N);
     const double npx = (double)N * M;
-    if (C == 2)
-        OHEM_LAUNCH(K_PX, npx * (4 * C + 5), ohem_px_kernel<2>, grid, dim3(256), 0, st, logits, labels, H, W, lstride, chunk,
-                    px_loss, ws.pos);
-    else
-        OHEM_LAUNCH(K_PX, npx * (4 * C + 5), ohem_px_kernel<4>, grid, dim3(256), 0, st, logits, labels, H, W, lstride, chunk,
-                    px_loss, ws.pos);
+    XV2_DISPATCH_C24(C, XV2_LAUNCH(ohem_kid(K_PX), npx * (4 * C + 5), ohem_px_kernel<CC>, grid, dim3(256), 0, st, logits, labels, H,
+                                   W, lstride, chunk, px_loss, ws.pos));
     const unsigned* vals = reinterpret_cast<const unsigned*>(px_loss);
     if (int rc = ohem_select(vals, N, M, nullptr, records, ws, B, st)) return rc;
-    OHEM_LAUNCH(K_SUM, npx * 4, ohem_sum_kernel, grid, dim3(256), 0, st, vals, M, chunk, records, ws.neg);
-    OHEM_LAUNCH(K_FINISH, 16.0 * N * B, ohem_finish_kernel, dim3(1), dim3(256), 0, st, ws.pos, ws.neg, N * B, N, records, sums,
-                loss);
+    XV2_LAUNCH(ohem_kid(K_SUM), npx * 4, ohem_sum_kernel, grid, dim3(256), 0, st, vals, M, chunk, records, ws.neg);
+    XV2_LAUNCH(ohem_kid(K_FINISH), 16.0 * N * B, ohem_finish_kernel, dim3(1), dim3(256), 0, st, ws.pos, ws.neg, N * B, N, records, sums,
+               loss);
     return XV2_OK;
 }
 
 extern "C" int xv2_ohem_backward(const float* logits, const uint8_t* labels, int N, int C, int H, int W, int lstride,
                                  const float* px_loss, const int* records, const double* sums, const float* gscale,
                                  float* dlogits, void* stream) {
-    XV2_CHECK_ARG(C == 2 || C == 4, "ohem: C=%d unsupported (2 or 4)", C);
+    if (int rc = loss_check("ohem", N, C, H, W, lstride)) return rc;
+    XV2_CHECK_ARG(logits && labels && px_loss && records && sums && gscale && dlogits, "ohem: null tensor");
     const int64_t M = (int64_t)H * W;
     if (int rc = ohem_check_shape(N, M)) return rc;
     hipStream_t st = (hipStream_t)stream;
@@ -393,11 +375,7 @@ extern "C" int xv2_ohem_backward(const float* logits, const uint8_t* labels, int
     const int grid = (int)std::min<int64_t>(cdiv(total, 256), 4096);
     const unsigned* vals = reinterpret_cast<const unsigned*>(px_loss);
     const double bytes = (double)total * (8 * C + 4);
-    if (C == 2)
-        OHEM_LAUNCH(K_BWD, bytes, ohem_bwd_kernel<2>, dim3(grid), dim3(256), 0, st, logits, labels, N, H, W, lstride, vals,
-                    records, sums, gscale, dlogits);
-    else
-        OHEM_LAUNCH(K_BWD, bytes, ohem_bwd_kernel<4>, dim3(grid), dim3(256), 0, st, logits, labels, N, H, W, lstride, vals,
-                    records, sums, gscale, dlogits);
+    XV2_DISPATCH_C24(C, XV2_LAUNCH(ohem_kid(K_BWD), bytes, ohem_bwd_kernel<CC>, dim3(grid), dim3(256), 0, st, logits, labels, N, H,
+                                   W, lstride, vals, records, sums, gscale, dlogits));
     return XV2_OK;
 }

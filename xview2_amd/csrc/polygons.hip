@@ -511,14 +511,6 @@ int rounds_for(int64_t E) {
 
 }  // namespace
 
-#define PG_LAUNCH(kid, bytes, ...)                                  \
-    do {                                                            \
-        xv2::prof_begin(kid, 0.0, (double)(bytes), st);             \
-        hipLaunchKernelGGL(__VA_ARGS__);                            \
-        xv2::prof_end(st);                                          \
-        XV2_CHECK_LAUNCH();                                         \
-    } while (0)
-
 enum { K_COUNT = 0, K_SCAN, K_TILES, K_INDEX, K_SUCC, K_MIN, K_CUT, K_RANK, K_LCOUNT, K_LSCAN, K_RINGS, K_VERTS };
 
 static int pg_kid(int k) {
@@ -556,8 +548,8 @@ extern "C" int xv2_polygon_count(const int32_t* labels, int B, int H, int W, voi
     const int npc = (int)pchunks_of(H, W);
     const double px = (double)B * H * W;
     u64* pchunk = static_cast<u64*>(workspace);
-    PG_LAUNCH(pg_kid(K_COUNT), px * 4, pg_count_kernel, dim3(npc, B), dim3(256), 0, st, labels, H, W, npc, pchunk);
-    PG_LAUNCH(pg_kid(K_SCAN), 16.0 * B * npc, pg_scan_kernel, dim3(B), dim3(SCAN_T), 0, st, pchunk, npc, counts);
+    XV2_LAUNCH(pg_kid(K_COUNT), px * 4, pg_count_kernel, dim3(npc, B), dim3(256), 0, st, labels, H, W, npc, pchunk);
+    XV2_LAUNCH(pg_kid(K_SCAN), 16.0 * B * npc, pg_scan_kernel, dim3(B), dim3(SCAN_T), 0, st, pchunk, npc, counts);
     return XV2_OK;
 }
 
@@ -579,31 +571,31 @@ extern "C" int xv2_polygon_trace(const int32_t* labels, int B, int H, int W, int
     const int npc = (int)pchunks_of(H, W);
     const double px = (double)B * H * W, ed = (double)total_edges;
     const unsigned E = (unsigned)total_edges;
-    PG_LAUNCH(pg_kid(K_COUNT), px * 4, pg_count_kernel, dim3(npc, B), dim3(256), 0, st, labels, H, W, npc, t.pchunk);
-    PG_LAUNCH(pg_kid(K_SCAN), 16.0 * B * npc, pg_scan_kernel, dim3(B), dim3(SCAN_T), 0, st, t.pchunk, npc,
-              reinterpret_cast<int64_t*>(t.tile_tot));
-    PG_LAUNCH(pg_kid(K_TILES), 28.0 * B, pg_tiles_kernel, dim3(1), dim3(256), 0, st, t.tile_tot, B, (long long)total_edges,
-              (long long)total_vertices, t.tile_eoff, t.hdr, ring_count, status);
+    XV2_LAUNCH(pg_kid(K_COUNT), px * 4, pg_count_kernel, dim3(npc, B), dim3(256), 0, st, labels, H, W, npc, t.pchunk);
+    XV2_LAUNCH(pg_kid(K_SCAN), 16.0 * B * npc, pg_scan_kernel, dim3(B), dim3(SCAN_T), 0, st, t.pchunk, npc,
+               reinterpret_cast<int64_t*>(t.tile_tot));
+    XV2_LAUNCH(pg_kid(K_TILES), 28.0 * B, pg_tiles_kernel, dim3(1), dim3(256), 0, st, t.tile_tot, B, (long long)total_edges,
+               (long long)total_vertices, t.tile_eoff, t.hdr, ring_count, status);
     if (total_edges == 0) return XV2_OK;
     const int R = rounds_for(total_edges), nec = (int)echunks_of(total_edges);
     const unsigned eb = (E + 255u) / 256u;
-    PG_LAUNCH(pg_kid(K_INDEX), px * 9 + ed * 4, pg_index_kernel, dim3(npc, B), dim3(256), 0, st, labels, H, W, npc, t.hdr,
-              t.tile_eoff, t.pchunk, E, t.pix_off, t.pix_em, t.einfo);
-    PG_LAUNCH(pg_kid(K_SUCC), px * 8 + ed * 12, pg_succ_kernel, dim3(npc, B), dim3(256), 0, st, labels, H, W, t.hdr,
-              t.pix_off, t.pix_em, E, t.succ, t.recA[0]);
+    XV2_LAUNCH(pg_kid(K_INDEX), px * 9 + ed * 4, pg_index_kernel, dim3(npc, B), dim3(256), 0, st, labels, H, W, npc, t.hdr,
+               t.tile_eoff, t.pchunk, E, t.pix_off, t.pix_em, t.einfo);
+    XV2_LAUNCH(pg_kid(K_SUCC), px * 8 + ed * 12, pg_succ_kernel, dim3(npc, B), dim3(256), 0, st, labels, H, W, t.hdr,
+               t.pix_off, t.pix_em, E, t.succ, t.recA[0]);
     for (int r = 0; r < R; ++r)
-        PG_LAUNCH(pg_kid(K_MIN), ed * 24, pg_min_kernel, dim3(eb), dim3(256), 0, st, t.hdr, r, E, t.recA[0], t.recA[1]);
-    PG_LAUNCH(pg_kid(K_CUT), ed * 36, pg_cut_kernel, dim3(eb), dim3(256), 0, st, t.hdr, R, E, W, t.recA[0], t.recA[1], t.succ,
-              t.einfo, t.lead, t.recB[0]);
+        XV2_LAUNCH(pg_kid(K_MIN), ed * 24, pg_min_kernel, dim3(eb), dim3(256), 0, st, t.hdr, r, E, t.recA[0], t.recA[1]);
+    XV2_LAUNCH(pg_kid(K_CUT), ed * 36, pg_cut_kernel, dim3(eb), dim3(256), 0, st, t.hdr, R, E, W, t.recA[0], t.recA[1], t.succ,
+               t.einfo, t.lead, t.recB[0]);
     for (int r = 0; r < R; ++r)
-        PG_LAUNCH(pg_kid(K_RANK), ed * 48, pg_rank_kernel, dim3(eb), dim3(256), 0, st, t.hdr, r, E, t.recB[0], t.recB[1]);
-    PG_LAUNCH(pg_kid(K_LCOUNT), ed * 8, pg_lcount_kernel, dim3(nec), dim3(256), 0, st, t.hdr, R, E, t.lead, t.recB[0],
-              t.recB[1], t.lchunk);
-    PG_LAUNCH(pg_kid(K_LSCAN), 16.0 * nec, pg_lscan_kernel, dim3(1), dim3(SCAN_T), 0, st, t.hdr, t.lchunk, nec);
-    PG_LAUNCH(pg_kid(K_RINGS), ed * 8, pg_rings_kernel, dim3(nec), dim3(256), 0, st, labels, B, H, W, t.hdr, R, E,
-              (long long)(total_vertices / 4), t.tile_eoff, t.lead, t.einfo, t.recB[0], t.recB[1], t.lchunk, t.voff, rings,
-              ring_count);
-    PG_LAUNCH(pg_kid(K_VERTS), ed * 28, pg_verts_kernel, dim3(eb), dim3(256), 0, st, t.hdr, R, E, (long long)total_vertices, W,
-              t.succ, t.lead, t.einfo, t.voff, t.recB[0], t.recB[1], verts);
+        XV2_LAUNCH(pg_kid(K_RANK), ed * 48, pg_rank_kernel, dim3(eb), dim3(256), 0, st, t.hdr, r, E, t.recB[0], t.recB[1]);
+    XV2_LAUNCH(pg_kid(K_LCOUNT), ed * 8, pg_lcount_kernel, dim3(nec), dim3(256), 0, st, t.hdr, R, E, t.lead, t.recB[0],
+               t.recB[1], t.lchunk);
+    XV2_LAUNCH(pg_kid(K_LSCAN), 16.0 * nec, pg_lscan_kernel, dim3(1), dim3(SCAN_T), 0, st, t.hdr, t.lchunk, nec);
+    XV2_LAUNCH(pg_kid(K_RINGS), ed * 8, pg_rings_kernel, dim3(nec), dim3(256), 0, st, labels, B, H, W, t.hdr, R, E,
+               (long long)(total_vertices / 4), t.tile_eoff, t.lead, t.einfo, t.recB[0], t.recB[1], t.lchunk, t.voff, rings,
+               ring_count);
+    XV2_LAUNCH(pg_kid(K_VERTS), ed * 28, pg_verts_kernel, dim3(eb), dim3(256), 0, st, t.hdr, R, E, (long long)total_vertices, W,
+               t.succ, t.lead, t.einfo, t.voff, t.recB[0], t.recB[1], verts);
     return XV2_OK;
 }

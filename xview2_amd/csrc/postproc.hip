@@ -354,15 +354,6 @@ size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
 
 }  // namespace
 
-// every launch is bracketed for the bench-time profiler (xv2_prof_enable; no-ops otherwise); bytes: algorithmic traffic
-#define PP_LAUNCH(kid, bytes, ...)                                  \
-    do {                                                            \
-        xv2::prof_begin(kid, 0.0, (double)(bytes), st);             \
-        hipLaunchKernelGGL(__VA_ARGS__);                            \
-        xv2::prof_end(st);                                          \
-        XV2_CHECK_LAUNCH();                                         \
-    } while (0)
-
 static int pp_kid(int k) {
     static const int ids[] = {xv2::prof_register("pp_fuse_kernel"), xv2::prof_register("pp_merge_kernel"),
                               xv2::prof_register("pp_compress_kernel"), xv2::prof_register("pp_vote_kernel"),
@@ -414,23 +405,23 @@ extern "C" int xv2_postprocess(const float* loc, const void* dmg, int dmg_kind, 
     const double px = (double)n, cin = dmg_kind == XV2_DMG_4CH ? 16 : dmg_kind == XV2_DMG_5CH ? 20 : 4;
     const double fuse_bytes = px * (4 + cin + 2 + (components ? 20 : 0));
     if (dmg_kind == XV2_DMG_4CH)
-        PP_LAUNCH(pp_kid(0), fuse_bytes, pp_fuse_kernel<K_4CH>, grid, dim3(256), 0, st, loc, dmg, H, W, comp, labels, counts,
-                  ipre, ipost, status);
+        XV2_LAUNCH(pp_kid(0), fuse_bytes, pp_fuse_kernel<K_4CH>, grid, dim3(256), 0, st, loc, dmg, H, W, comp, labels, counts,
+                   ipre, ipost, status);
     else if (dmg_kind == XV2_DMG_5CH)
-        PP_LAUNCH(pp_kid(0), fuse_bytes, pp_fuse_kernel<K_5CH>, grid, dim3(256), 0, st, loc, dmg, H, W, comp, labels, counts,
-                  ipre, ipost, status);
+        XV2_LAUNCH(pp_kid(0), fuse_bytes, pp_fuse_kernel<K_5CH>, grid, dim3(256), 0, st, loc, dmg, H, W, comp, labels, counts,
+                   ipre, ipost, status);
     else
-        PP_LAUNCH(pp_kid(0), fuse_bytes, pp_fuse_kernel<K_LABEL>, grid, dim3(256), 0, st, loc, dmg, H, W, comp, labels,
-                  counts, ipre, ipost, status);
+        XV2_LAUNCH(pp_kid(0), fuse_bytes, pp_fuse_kernel<K_LABEL>, grid, dim3(256), 0, st, loc, dmg, H, W, comp, labels,
+                   counts, ipre, ipost, status);
     if (components) {
-        PP_LAUNCH(pp_kid(1), 8.0 * 128 * grid.x * grid.y * B, pp_merge_kernel, grid, dim3(128), 0, st, labels, H, W);
-        PP_LAUNCH(pp_kid(2), px * 9, pp_compress_kernel<true>, grid, dim3(256), 0, st, labels, ipost, H, W,
-                  reinterpret_cast<unsigned*>(counts));
-        PP_LAUNCH(pp_kid(3), px * 8, pp_vote_kernel<true>, grid, dim3(256), 0, st, ipre, ipost, labels, counts, H, W,
-                  rate ? rate / 2 : 0, pre, post);
+        XV2_LAUNCH(pp_kid(1), 8.0 * 128 * grid.x * grid.y * B, pp_merge_kernel, grid, dim3(128), 0, st, labels, H, W);
+        XV2_LAUNCH(pp_kid(2), px * 9, pp_compress_kernel<true>, grid, dim3(256), 0, st, labels, ipost, H, W,
+                   reinterpret_cast<unsigned*>(counts));
+        XV2_LAUNCH(pp_kid(3), px * 8, pp_vote_kernel<true>, grid, dim3(256), 0, st, ipre, ipost, labels, counts, H, W,
+                   rate ? rate / 2 : 0, pre, post);
     } else if (rate) {
-        PP_LAUNCH(pp_kid(3), px * 4, pp_vote_kernel<false>, grid, dim3(256), 0, st, ipre, ipost, labels, counts, H, W,
-                  rate / 2, pre, post);
+        XV2_LAUNCH(pp_kid(3), px * 4, pp_vote_kernel<false>, grid, dim3(256), 0, st, ipre, ipost, labels, counts, H, W,
+                   rate / 2, pre, post);
     }
     return XV2_OK;
 }
@@ -443,10 +434,10 @@ extern "C" int xv2_label_components(const uint8_t* mask, int B, int H, int W, vo
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((W + RG - 1) / RG, (H + RG - 1) / RG, B);
     const double px = (double)B * H * W;
-    PP_LAUNCH(pp_kid(0), px * 5, pp_fuse_kernel<K_MASK>, grid, dim3(256), 0, st, nullptr, mask, H, W, 1, labels, nullptr,
-              nullptr, nullptr, nullptr);
-    PP_LAUNCH(pp_kid(1), 8.0 * 128 * grid.x * grid.y * B, pp_merge_kernel, grid, dim3(128), 0, st, labels, H, W);
-    PP_LAUNCH(pp_kid(2), px * 8, pp_compress_kernel<false>, grid, dim3(256), 0, st, labels, nullptr, H, W, nullptr);
+    XV2_LAUNCH(pp_kid(0), px * 5, pp_fuse_kernel<K_MASK>, grid, dim3(256), 0, st, nullptr, mask, H, W, 1, labels, nullptr,
+               nullptr, nullptr, nullptr);
+    XV2_LAUNCH(pp_kid(1), 8.0 * 128 * grid.x * grid.y * B, pp_merge_kernel, grid, dim3(128), 0, st, labels, H, W);
+    XV2_LAUNCH(pp_kid(2), px * 8, pp_compress_kernel<false>, grid, dim3(256), 0, st, labels, nullptr, H, W, nullptr);
     return XV2_OK;
 }
 
@@ -456,7 +447,7 @@ extern "C" int xv2_xview2_counts(const uint8_t* lp, const uint8_t* dp, const uin
     XV2_CHECK_ARG(lp && dp && lt && dt && counts, "xview2_counts: null tensor");
     const int gx = (int)std::max<int64_t>(1, std::min<int64_t>(xv2::cdiv(hw, 256 * 16), 256));
     hipStream_t st = (hipStream_t)stream;
-    PP_LAUNCH(pp_kid(4), 4.0 * B * hw, xview2_counts_kernel, dim3(gx, B), dim3(256), 0, st, lp, dp, lt, dt, hw,
-              reinterpret_cast<unsigned long long*>(counts));
+    XV2_LAUNCH(pp_kid(4), 4.0 * B * hw, xview2_counts_kernel, dim3(gx, B), dim3(256), 0, st, lp, dp, lt, dt, hw,
+               reinterpret_cast<unsigned long long*>(counts));
     return XV2_OK;
 }

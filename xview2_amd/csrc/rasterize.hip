@@ -100,14 +100,6 @@ bool sizes_ok(int B, int H, int W) {
 
 }  // namespace
 
-#define RS_LAUNCH(kid, bytes, ...)                                  \
-    do {                                                            \
-        xv2::prof_begin(kid, 0.0, (double)(bytes), st);             \
-        hipLaunchKernelGGL(__VA_ARGS__);                            \
-        xv2::prof_end(st);                                          \
-        XV2_CHECK_LAUNCH();                                         \
-    } while (0)
-
 extern "C" size_t xv2_rasterize_workspace(int B, int H, int W) {
     if (!sizes_ok(B, H, W)) return 0;
     return 4 * (size_t)B * H * W;
@@ -184,10 +176,10 @@ extern "C" int xv2_rasterize_polygons(const int32_t* dev_tables, const int32_t* 
     XV2_CHECK_HIP(hipMemsetAsync(order, 0, 4 * (size_t)total, st));
     const int32_t* feats = dev_tables + 4 * n_edges;
     const int32_t* work = feats + (int64_t)FEAT_COLS * n_features;
-    RS_LAUNCH(rs_kid(0), 16.0 * n_work + 4096.0 * n_work, rs_cover_kernel, dim3((unsigned)n_work), dim3(256), 0, st,
-              reinterpret_cast<const int4*>(dev_tables), (long long)n_edges, feats, n_features,
-              reinterpret_cast<const int4*>(work), frac_bits, off, B, H, W, order);
-    RS_LAUNCH(rs_kid(1), 5.0 * total, rs_resolve_kernel, dim3((unsigned)((total + 1023) / 1024)), dim3(256), 0, st, order, feats,
-              n_features, total, out);
+    XV2_LAUNCH(rs_kid(0), 16.0 * n_work + 4096.0 * n_work, rs_cover_kernel, dim3((unsigned)n_work), dim3(256), 0, st,
+               reinterpret_cast<const int4*>(dev_tables), (long long)n_edges, feats, n_features,
+               reinterpret_cast<const int4*>(work), frac_bits, off, B, H, W, order);
+    XV2_LAUNCH(rs_kid(1), 5.0 * total, rs_resolve_kernel, dim3((unsigned)((total + 1023) / 1024)), dim3(256), 0, st, order, feats,
+               n_features, total, out);
     return XV2_OK;
 }

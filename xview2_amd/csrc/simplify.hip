@@ -517,14 +517,6 @@ bool sizes_ok(int64_t n_rings, int64_t V) {
 
 }  // namespace
 
-#define SP_LAUNCH(kid, bytes, ...)                                  \
-    do {                                                            \
-        xv2::prof_begin(kid, 0.0, (double)(bytes), st);             \
-        hipLaunchKernelGGL(__VA_ARGS__);                            \
-        xv2::prof_end(st);                                          \
-        XV2_CHECK_LAUNCH();                                         \
-    } while (0)
-
 static int sp_kid(int k) {
     static const int ids[] = {xv2::prof_register("sp_simplify_kernel"), xv2::prof_register("sp_offsets_kernel"),
                               xv2::prof_register("sp_write_kernel")};
@@ -555,13 +547,13 @@ extern "C" int xv2_polygon_simplify(const int64_t* rings, const int32_t* verts, 
     const int2* v2 = reinterpret_cast<const int2*>(verts);
     const int64_t n_blocks = (n_rings + RC - 1) / RC;
     if (n_rings > 0)
-        SP_LAUNCH(sp_kid(0), rb + 2.5 * vb, sp_simplify_kernel, dim3((unsigned)n_blocks), dim3(T), 0, st, rings,
-                  v2, (i64)n_rings, (i64)total_vertices, (u64)q * (u64)q, w);
-    SP_LAUNCH(sp_kid(1), 16.0 * (double)n_blocks, sp_offsets_kernel, dim3(1), dim3(SCAN_T), 0, st, w.bsum, (i64)n_blocks,
-              out_total);
+        XV2_LAUNCH(sp_kid(0), rb + 2.5 * vb, sp_simplify_kernel, dim3((unsigned)n_blocks), dim3(T), 0, st, rings,
+                   v2, (i64)n_rings, (i64)total_vertices, (u64)q * (u64)q, w);
+    XV2_LAUNCH(sp_kid(1), 16.0 * (double)n_blocks, sp_offsets_kernel, dim3(1), dim3(SCAN_T), 0, st, w.bsum, (i64)n_blocks,
+               out_total);
     const int64_t flat = n_rings * COLS > total_vertices ? n_rings * COLS : total_vertices;
     if (flat > 0)
-        SP_LAUNCH(sp_kid(2), 2.0 * rb + 2.5 * vb, sp_write_kernel, dim3((unsigned)((flat + 255) / 256)), dim3(256), 0, st, rings,
-                  (i64)n_rings, (i64)total_vertices, w, out_rings, reinterpret_cast<int2*>(out_verts));
+        XV2_LAUNCH(sp_kid(2), 2.0 * rb + 2.5 * vb, sp_write_kernel, dim3((unsigned)((flat + 255) / 256)), dim3(256), 0, st, rings,
+                   (i64)n_rings, (i64)total_vertices, w, out_rings, reinterpret_cast<int2*>(out_verts));
     return XV2_OK;
 }

@@ -150,14 +150,6 @@ __global__ void __launch_bounds__(SORT_THREADS) sort_scatter_kernel(const unsign
     }
 }
 
-#define SORT_LAUNCH(kid, bytes, ...)                    \
-    do {                                                \
-        prof_begin(sort_kid(kid), 0.0, (double)(bytes), st); \
-        hipLaunchKernelGGL(__VA_ARGS__);                \
-        prof_end(st);                                   \
-        XV2_CHECK_LAUNCH();                             \
-    } while (0)
-
 enum { K_HIST, K_SCAN, K_SCATTER };
 static int sort_kid(int k) {
     static const int ids[] = {prof_register("sort_hist_kernel"), prof_register("sort_scan_kernel"),
@@ -193,10 +185,10 @@ extern "C" int xv2_sort_u32(const uint32_t* keys, uint32_t* out, int R, int64_t 
     for (int pass = 0; pass < SORT_PASSES; ++pass) {
         unsigned* dst = (pass & 1) ? out : tmp;
         const int shift = 8 * pass;
-        SORT_LAUNCH(K_HIST, kb + tb, sort_hist_kernel, grid, dim3(SORT_THREADS), 0, st, src, M, p.tpb, shift, table);
-        SORT_LAUNCH(K_SCAN, 2.0 * tb, sort_scan_kernel, dim3(SORT_DIGITS, R), dim3(SORT_THREADS), 0, st, table, p.nb, totals);
-        SORT_LAUNCH(K_SCATTER, 2.0 * kb + tb, sort_scatter_kernel, grid, dim3(SORT_THREADS), 0, st, src, dst, M, p.ntiles, p.tpb,
-                    shift, table, totals);
+        XV2_LAUNCH(sort_kid(K_HIST), kb + tb, sort_hist_kernel, grid, dim3(SORT_THREADS), 0, st, src, M, p.tpb, shift, table);
+        XV2_LAUNCH(sort_kid(K_SCAN), 2.0 * tb, sort_scan_kernel, dim3(SORT_DIGITS, R), dim3(SORT_THREADS), 0, st, table, p.nb, totals);
+        XV2_LAUNCH(sort_kid(K_SCATTER), 2.0 * kb + tb, sort_scatter_kernel, grid, dim3(SORT_THREADS), 0, st, src, dst, M, p.ntiles, p.tpb,
+                   shift, table, totals);
         src = dst;
     }
     return XV2_OK;

@@ -243,14 +243,6 @@ Layout layout(void* workspace, int B, int H, int W) {
 
 }  // namespace
 
-#define SP_LAUNCH(kid, bytes, ...)                                  \
-    do {                                                            \
-        xv2::prof_begin(kid, 0.0, (double)(bytes), st);             \
-        hipLaunchKernelGGL(__VA_ARGS__);                            \
-        xv2::prof_end(st);                                          \
-        XV2_CHECK_LAUNCH();                                         \
-    } while (0)
-
 static int sp_kid(int k) {
     static const int ids[] = {xv2::prof_register("sp_edt_kernel"), xv2::prof_register("sp_init_kernel"),
                               xv2::prof_register("sp_grow_kernel"), xv2::prof_register("sp_finish_kernel")};
@@ -276,8 +268,8 @@ extern "C" int xv2_edt_sq(const uint8_t* mask, int B, int H, int W, int cap, uin
     XV2_CHECK_ARG(mask && d2, "edt_sq: null tensor");
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((W + RG - 1) / RG, (H + RG - 1) / RG, B);
-    SP_LAUNCH(sp_kid(0), 3.0 * B * H * W, sp_edt_kernel<false>, grid, dim3(256), edt_lds(cap), st, mask, H, W, cap, 0, d2,
-              nullptr);
+    XV2_LAUNCH(sp_kid(0), 3.0 * B * H * W, sp_edt_kernel<false>, grid, dim3(256), edt_lds(cap), st, mask, H, W, cap, 0, d2,
+               nullptr);
     return XV2_OK;
 }
 
@@ -298,12 +290,12 @@ extern "C" int xv2_split_seed(const uint8_t* mask, int B, int H, int W, int r2, 
     const int64_t n = (int64_t)B * H * W;
     const int cap = cap_of(r2);
     const dim3 grid((W + RG - 1) / RG, (H + RG - 1) / RG, B);
-    SP_LAUNCH(sp_kid(0), 2.0 * n, sp_edt_kernel<true>, grid, dim3(256), edt_lds(cap), st, mask, H, W, cap, r2, nullptr,
-              l.seed);
+    XV2_LAUNCH(sp_kid(0), 2.0 * n, sp_edt_kernel<true>, grid, dim3(256), edt_lds(cap), st, mask, H, W, cap, r2, nullptr,
+               l.seed);
     if (int rc = xv2_label_components(l.seed, B, H, W, nullptr, l.labels, stream)) return rc;
     const int64_t hw = (int64_t)H * W;
-    SP_LAUNCH(sp_kid(1), 13.0 * n, sp_init_kernel, dim3((unsigned)xv2::cdiv(hw, 256), B), dim3(256), 0, st, mask, l.labels, hw,
-              l.a, l.flags[0], l.regions);
+    XV2_LAUNCH(sp_kid(1), 13.0 * n, sp_init_kernel, dim3((unsigned)xv2::cdiv(hw, 256), B), dim3(256), 0, st, mask, l.labels, hw,
+               l.a, l.flags[0], l.regions);
     return XV2_OK;
 }
 
@@ -320,8 +312,8 @@ extern "C" int xv2_split_grow(const uint8_t* mask, int B, int H, int W, int swee
     XV2_CHECK_HIP(hipMemsetAsync(pending, 0, sizeof(int32_t), st));
     u64 *src = l.a, *dst = l.b;
     for (int s = 0; s < sweeps; ++s) {
-        SP_LAUNCH(sp_kid(2), 16.0 * n, sp_grow_kernel, grid, dim3(256), 0, st, src, dst, H, W, l.flags[s & 1],
-                  l.flags[(s + 1) & 1], s == sweeps - 1 ? pending : nullptr);
+        XV2_LAUNCH(sp_kid(2), 16.0 * n, sp_grow_kernel, grid, dim3(256), 0, st, src, dst, H, W, l.flags[s & 1],
+                   l.flags[(s + 1) & 1], s == sweeps - 1 ? pending : nullptr);
         u64* t = src;
         src = dst;
         dst = t;
@@ -342,7 +334,7 @@ extern "C" int xv2_split_finish(const uint8_t* mask, int B, int H, int W, void* 
     hipStream_t st = (hipStream_t)stream;
     const Layout l = layout(workspace, B, H, W);
     const int64_t hw = (int64_t)H * W;
-    SP_LAUNCH(sp_kid(3), (labels ? 14.0 : 10.0) * B * hw, sp_finish_kernel, dim3((unsigned)xv2::cdiv(hw, 256), B), dim3(256), 0, st,
-              mask, l.a, H, W, out, labels);
+    XV2_LAUNCH(sp_kid(3), (labels ? 14.0 : 10.0) * B * hw, sp_finish_kernel, dim3((unsigned)xv2::cdiv(hw, 256), B), dim3(256), 0, st,
+               mask, l.a, H, W, out, labels);
     return XV2_OK;
 }

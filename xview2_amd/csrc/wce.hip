@@ -98,23 +98,10 @@ __global__ void __launch_bounds__(256) border_weights_kernel(const uint16_t* __r
         out[i] = wce_border(d1[i], d2[i], w0, sigma);
 }
 
-// index of the label (and of its D1 / D2 entries) behind pixel (n, h, w) of a head: label_at's arithmetic
-__device__ __forceinline__ int64_t wce_label_index(int64_t n, int h, int w, int H, int W, int ls) {
-    return (n * (int64_t)H * ls + (int64_t)h * ls) * ((int64_t)W * ls) + (int64_t)w * ls;
-}
-
 // the pixel's class, or -1 for a pixel that takes no part (post: label 0; a class beyond C)
 __device__ __forceinline__ int wce_class(int y, int post, int C) {
     if (post) y -= 1;
     return y < C ? y : -1;
-}
-
-template <int C>
-__device__ __forceinline__ float wce_pick(const float (&v)[C], int c) {
-    float r = v[0];
-#pragma unroll
-    for (int k = 1; k < C; ++k) r = (c == k) ? v[k] : r;
-    return r;
 }
 
 template <int C>
@@ -128,49 +115,32 @@ __global__ void __launch_bounds__(256) wce_fwd_kernel(const float* __restrict__ 
     float cw[C];
 #pragma unroll
     for (int c = 0; c < C; ++c) cw[c] = class_w[c];
-    float a0 = 0.f, a1 = 0.f;
+    float a[2] = {0.f, 0.f};      // sum of w l, sum of w
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t n = i / hw, q = i - n * hw;
-        const int h = (int)(q / W), w = (int)(q - (int64_t)h * W);
-        const int64_t li = wce_label_index(n, h, w, H, W, ls);
+        const Px px = px_decode<C>(i, hw, W);
+        const int64_t li = label_index(px.n, px.h, px.w, H, W, ls);      // of the label and of its D1 / D2 entries
         const int cls = wce_class(labels[li], post, C);
         if (cls < 0) continue;
-        const float wt = wce_weight(wce_pick<C>(cw, cls), d1 ? wce_border(d1[li], d2[li], w0, sigma) : 0.f);
-        const int64_t base = n * C * hw + q;
+        const float wt = wce_weight(pick<C>(cw, cls), d1 ? wce_border(d1[li], d2[li], w0, sigma) : 0.f);
+        const int64_t base = px.base;
         float p[C], lse;
         softmax_px<C>(logits, base, hw, p, lse);
         const float l = lse - logits[base + cls * hw];
-        a0 += wt * l;
-        a1 += wt;
+        a[0] += wt * l;
+        a[1] += wt;
     }
-    const double s0 = wave_sum((double)a0), s1 = wave_sum((double)a1);
-    if ((threadIdx.x & 63) == 0) {
-        sh[threadIdx.x >> 6][0] = s0;
-        sh[threadIdx.x >> 6][1] = s1;
-    }
-    __syncthreads();
-    if (threadIdx.x < 2)
-        part[(size_t)blockIdx.x * 2 + threadIdx.x] = sh[0][threadIdx.x] + sh[1][threadIdx.x] + sh[2][threadIdx.x] + sh[3][threadIdx.x];
+    block_sum_store(a, sh, part + (size_t)blockIdx.x * 2);
 }
 
 // one block: the block partials strided over the threads, then across them in a fixed order
 __global__ void __launch_bounds__(256) wce_finish_kernel(const double* __restrict__ part, int nblocks, double* __restrict__ sums,
                                                          float* __restrict__ loss) {
-    __shared__ double sh[4][2];
-    double s0 = 0.0, s1 = 0.0;
-    for (int b = threadIdx.x; b < nblocks; b += 256) {
-        s0 += part[(size_t)b * 2];
-        s1 += part[(size_t)b * 2 + 1];
-    }
-    s0 = wave_sum(s0);
-    s1 = wave_sum(s1);
-    if ((threadIdx.x & 63) == 0) {
-        sh[threadIdx.x >> 6][0] = s0;
-        sh[threadIdx.x >> 6][1] = s1;
-    }
+    __shared__ double sh[2][4];
+    strided_wave_total(part, nblocks, 2, sh[0]);
+    strided_wave_total(part + 1, nblocks, 2, sh[1]);
     __syncthreads();
     if (threadIdx.x != 0) return;
-    const double wl = sh[0][0] + sh[1][0] + sh[2][0] + sh[3][0], sw = sh[0][1] + sh[1][1] + sh[2][1] + sh[3][1];
+    const double wl = wave4_total(sh[0]), sw = wave4_total(sh[1]);
     sums[0] = wl;
     sums[1] = sw;
     loss[0] = sw > 0.0 ? (float)(wl / sw) : 0.f;
@@ -192,17 +162,15 @@ __global__ void __launch_bounds__(256) wce_bwd_kernel(const float* __restrict__ 
 #pragma unroll
     for (int c = 0; c < C; ++c) cw[c] = class_w[c];
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t n = i / hw, q = i - n * hw;
-        const int h = (int)(q / W), w = (int)(q - (int64_t)h * W);
-        const int64_t li = wce_label_index(n, h, w, H, W, ls);
+        const Px px = px_decode<C>(i, hw, W);
+        const int64_t li = label_index(px.n, px.h, px.w, H, W, ls);
         const int cls = wce_class(labels[li], post, C);
-        const int64_t base = n * C * hw + q;
+        const int64_t base = px.base;
         if (cls < 0 || !live) {
-#pragma unroll
-            for (int c = 0; c < C; ++c) dlogits[base + c * hw] = 0.f;
+            zero_px<C>(dlogits, base, hw);
             continue;
         }
-        const float wt = wce_weight(wce_pick<C>(cw, cls), d1 ? wce_border(d1[li], d2[li], w0, sigma) : 0.f);
+        const float wt = wce_weight(pick<C>(cw, cls), d1 ? wce_border(d1[li], d2[li], w0, sigma) : 0.f);
         float p[C], lse;
         softmax_px<C>(logits, base, hw, p, lse);
         const float k = gs * (wt * inv);
@@ -210,14 +178,6 @@ __global__ void __launch_bounds__(256) wce_bwd_kernel(const float* __restrict__ 
         for (int c = 0; c < C; ++c) dlogits[base + c * hw] = k * (p[c] - ((cls == c) ? 1.f : 0.f));
     }
 }
-
-#define WCE_LAUNCH(kid, bytes, ...)                         \
-    do {                                                    \
-        prof_begin(wce_kid(kid), 0.0, (double)(bytes), st); \
-        hipLaunchKernelGGL(__VA_ARGS__);                    \
-        prof_end(st);                                       \
-        XV2_CHECK_LAUNCH();                                 \
-    } while (0)
 
 enum { K_DIST, K_MAP, K_FWD, K_FINISH, K_BWD };
 static int wce_kid(int k) {
@@ -242,10 +202,9 @@ static int map_check(const char* what, float w0, float sigma) {
 }
 
 static int wce_check(int N, int C, int H, int W, int lstride, int post, const void* d1, const void* d2, float w0, float sigma) {
-    XV2_CHECK_ARG(C == 2 || C == 4, "wce: C=%d unsupported (2 or 4)", C);
-    XV2_CHECK_ARG(N >= 1 && H >= 1 && W >= 1 && N <= 65535, "wce: bad shape N=%d H=%d W=%d", N, H, W);
+    if (int rc = loss_check("wce", N, C, H, W, lstride)) return rc;
+    XV2_CHECK_ARG(N <= 65535, "wce: N=%d images unsupported (<= 65535)", N);
     XV2_CHECK_ARG((int64_t)H * W < ((int64_t)1 << 30), "wce: H*W=%lld pixels per image unsupported (< 2^30)", (long long)H * W);
-    XV2_CHECK_ARG(lstride >= 1, "wce: bad lstride=%d", lstride);
     XV2_CHECK_ARG((d1 == nullptr) == (d2 == nullptr), "wce: d1 and d2 come together (both NULL: no border term)");
     if (d1) {
         XV2_CHECK_ARG(!post, "wce: the border term is defined for post == 0 only (post=%d with distance maps)", post);
@@ -273,7 +232,7 @@ extern "C" int xv2_border_distances(const uint8_t* labels, int B, int H, int W, 
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)cdiv(W, BT), (unsigned)cdiv(H, BT), (unsigned)B);
     const int S = BT + 2 * R;
-    WCE_LAUNCH(K_DIST, (double)B * H * W * 8, border_dist_kernel, grid, dim3(256), (size_t)S * S * sizeof(int), st, comp, H, W,
+    XV2_LAUNCH(wce_kid(K_DIST), (double)B * H * W * 8, border_dist_kernel, grid, dim3(256), (size_t)S * S * sizeof(int), st, comp, H, W,
                R, d1, d2);
     return XV2_OK;
 }
@@ -285,7 +244,7 @@ extern "C" int xv2_border_weights(const uint16_t* d1, const uint16_t* d2, int64_
     XV2_CHECK_ARG(d1 && d2 && out, "border_weights: null tensor");
     hipStream_t st = (hipStream_t)stream;
     const int grid = (int)std::min<int64_t>(cdiv(n, 256), 4096);
-    WCE_LAUNCH(K_MAP, (double)n * 8, border_weights_kernel, dim3(grid), dim3(256), 0, st, d1, d2, n, w0, sigma, out);
+    XV2_LAUNCH(wce_kid(K_MAP), (double)n * 8, border_weights_kernel, dim3(grid), dim3(256), 0, st, d1, d2, n, w0, sigma, out);
     return XV2_OK;
 }
 
@@ -304,13 +263,9 @@ extern "C" int xv2_wce_forward(const float* logits, const uint8_t* labels, int N
     const int grid = (int)std::min<int64_t>(cdiv(total, 256), WCE_BLOCKS);
     double* part = reinterpret_cast<double*>(workspace);
     const double bytes = (double)total * (4 * C + 1 + (d1 ? 4 : 0));
-    if (C == 2)
-        WCE_LAUNCH(K_FWD, bytes, wce_fwd_kernel<2>, dim3(grid), dim3(256), 0, st, logits, labels, N, H, W, lstride, post,
-                   class_w, d1, d2, w0, sigma, part);
-    else
-        WCE_LAUNCH(K_FWD, bytes, wce_fwd_kernel<4>, dim3(grid), dim3(256), 0, st, logits, labels, N, H, W, lstride, post,
-                   class_w, d1, d2, w0, sigma, part);
-    WCE_LAUNCH(K_FINISH, 16.0 * grid, wce_finish_kernel, dim3(1), dim3(256), 0, st, part, grid, sums, loss);
+    XV2_DISPATCH_C24(C, XV2_LAUNCH(wce_kid(K_FWD), bytes, wce_fwd_kernel<CC>, dim3(grid), dim3(256), 0, st, logits, labels, N, H, W,
+                                   lstride, post, class_w, d1, d2, w0, sigma, part));
+    XV2_LAUNCH(wce_kid(K_FINISH), 16.0 * grid, wce_finish_kernel, dim3(1), dim3(256), 0, st, part, grid, sums, loss);
     return XV2_OK;
 }
 
@@ -323,11 +278,7 @@ extern "C" int xv2_wce_backward(const float* logits, const uint8_t* labels, int 
     const int64_t total = (int64_t)N * H * W;
     const int grid = (int)std::min<int64_t>(cdiv(total, 256), WCE_BWD_BLOCKS);
     const double bytes = (double)total * (8 * C + 1 + (d1 ? 4 : 0));
-    if (C == 2)
-        WCE_LAUNCH(K_BWD, bytes, wce_bwd_kernel<2>, dim3(grid), dim3(256), 0, st, logits, labels, N, H, W, lstride, post,
-                   class_w, d1, d2, w0, sigma, sums, gscale, dlogits);
-    else
-        WCE_LAUNCH(K_BWD, bytes, wce_bwd_kernel<4>, dim3(grid), dim3(256), 0, st, logits, labels, N, H, W, lstride, post,
-                   class_w, d1, d2, w0, sigma, sums, gscale, dlogits);
+    XV2_DISPATCH_C24(C, XV2_LAUNCH(wce_kid(K_BWD), bytes, wce_bwd_kernel<CC>, dim3(grid), dim3(256), 0, st, logits, labels, N, H, W,
+                                   lstride, post, class_w, d1, d2, w0, sigma, sums, gscale, dlogits));
     return XV2_OK;
 }

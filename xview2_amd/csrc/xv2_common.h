@@ -33,6 +33,16 @@ void prof_end(hipStream_t stream);
 
 #define XV2_CHECK_LAUNCH() XV2_CHECK_HIP(hipGetLastError())
 
+// a launch bracketed for the bench-time profiler (xv2_prof_enable; no-ops otherwise) and checked; kid: the id prof_register
+// gave the kernel's name, bytes: algorithmic traffic
+#define XV2_LAUNCH(kid, bytes, kernel, grid, block, shmem, st, ...)                 \
+    do {                                                                            \
+        xv2::prof_begin(kid, 0.0, (double)(bytes), st);                             \
+        hipLaunchKernelGGL(kernel, grid, block, shmem, st, __VA_ARGS__);            \
+        xv2::prof_end(st);                                                          \
+        XV2_CHECK_LAUNCH();                                                         \
+    } while (0)
+
 __host__ __device__ static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 __device__ __forceinline__ float apply_act(float v, int act) {
@@ -225,6 +235,11 @@ __device__ __forceinline__ double wave_sum(double v) {
     return v;
 }
 __device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ int wave_sum(int v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;

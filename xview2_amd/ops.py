@@ -2008,16 +2008,28 @@ class SplitAttentionFn(torch.autograd.Function):
         return dx, dw1.reshape(s1), db1, dg1, dbe1, dw2.reshape(s2), db2, None, None
 
 
+def _as_u8(labels):
+    labels = labels.contiguous()
+    return labels if labels.dtype == torch.uint8 else labels.to(torch.uint8)
+
+
+def _loss_inputs(logits, labels):
+    """logits and labels as the loss kernels read them: both contiguous, the labels uint8"""
+    _need_cuda(logits)
+    return logits.contiguous(), _as_u8(labels)
+
+
+def _gscale(gout):
+    """the incoming gradient of a scalar loss as the fp32 [1] tensor the backward kernels read"""
+    return gout.reshape(1).to(torch.float32).contiguous()
+
+
 class LossFn(torch.autograd.Function):
     """Composed Dice/Focal/CE loss on NCHW logits (model/loss.py:85-101)."""
 
     @staticmethod
     def forward(ctx, logits, labels, terms, post, lstride):
-        _need_cuda(logits)
-        logits = logits.contiguous()
-        labels = labels.contiguous()
-        if labels.dtype != torch.uint8:
-            labels = labels.to(torch.uint8)
+        logits, labels = _loss_inputs(logits, labels)
         N, C, H, W = logits.shape
         acc = torch.empty((32,), dtype=torch.float64, device=logits.device)
         loss = _f32((1,), logits)
@@ -2033,7 +2045,7 @@ class LossFn(torch.autograd.Function):
         terms, post, lstride = ctx.cfg
         N, C, H, W = logits.shape
         d = torch.empty_like(logits)
-        gs = gout.reshape(1).to(torch.float32).contiguous()
+        gs = _gscale(gout)
         call("xv2_loss_backward", logits, labels, N, C, H, W, lstride, 1 if post else 0, terms, acc, gs, 1.0, d)
         return d, None, None, None, None
 
@@ -2041,11 +2053,7 @@ class LossFn(torch.autograd.Function):
 def ohem_forward(logits, labels, lstride=1):
     """xv2_ohem_forward: (loss [1], px_loss [N, H*W], records [N, 8] int32, sums [3] float64, logits, labels), the last two
     as handed to the kernels.  Every output is a fresh tensor; only the histogram workspace is scratch."""
-    _need_cuda(logits)
-    logits = logits.contiguous()
-    labels = labels.contiguous()
-    if labels.dtype != torch.uint8:
-        labels = labels.to(torch.uint8)
+    logits, labels = _loss_inputs(logits, labels)
     N, C, H, W = logits.shape
     px_loss = _f32((N, H * W), logits)
     rec = torch.empty((N, 8), dtype=torch.int32, device=logits.device)
@@ -2074,7 +2082,7 @@ class OhemFn(torch.autograd.Function):
         logits, labels, px_loss, rec, sums = ctx.saved_tensors
         N, C, H, W = logits.shape
         d = torch.empty_like(logits)
-        gs = gout.reshape(1).to(torch.float32).contiguous()
+        gs = _gscale(gout)
         call("xv2_ohem_backward", logits, labels, N, C, H, W, ctx.lstride, px_loss, rec, sums, gs, d)
         return d, None, None
 
@@ -2114,11 +2122,7 @@ def lovasz_forward(logits, labels, lstride=1, post=False, class_mask=None):
     """xv2_lovasz_forward: (loss [1], keys [C, N*H*W] int32, sorted [C, N*H*W] int32, records [C, 4] int32, sums [5] float64,
     logits), the last as handed to the kernels.  Every output is a fresh tensor; only the workspace is scratch.  keys and
     sorted hold uint32 bit patterns."""
-    _need_cuda(logits)
-    logits = logits.contiguous()
-    labels = labels.contiguous()
-    if labels.dtype != torch.uint8:
-        labels = labels.to(torch.uint8)
+    logits, labels = _loss_inputs(logits, labels)
     N, C, H, W = logits.shape
     if class_mask is None:
         class_mask = lovasz_class_mask(C, post)
@@ -2148,7 +2152,7 @@ class LovaszFn(torch.autograd.Function):
         logits, keys, srt, rec, sums = ctx.saved_tensors
         N, C, H, W = logits.shape
         d = torch.empty_like(logits)
-        gs = gout.reshape(1).to(torch.float32).contiguous()
+        gs = _gscale(gout)
         call("xv2_lovasz_backward", logits, N, C, H, W, keys, srt, rec, sums, gs, d)
         return d, None, None, None
 
@@ -2160,8 +2164,7 @@ def _u8_labels(what, labels):
     _need_cuda(labels)
     if labels.dim() != 3:
         raise ValueError("%s: labels must be [B,H,W], got %s" % (what, tuple(labels.shape)))
-    labels = labels.contiguous()
-    return labels if labels.dtype == torch.uint8 else labels.to(torch.uint8)
+    return _as_u8(labels)
 
 
 def border_distances(labels, R):
@@ -2202,9 +2205,7 @@ def _wce_border_args(border, labels):
 def wce_forward(logits, labels, class_w, lstride=1, post=False, border=None):
     """xv2_wce_forward: (loss [1], sums [2] float64, logits, labels), the last two as handed to the kernels.  class_w: fp32 [C]
     on the device.  border: None or (d1, d2, w0, sigma) with the maps of border_distances(labels, R)."""
-    _need_cuda(logits)
-    logits = logits.contiguous()
-    labels = _u8_labels("wce", labels)
+    logits, labels = _loss_inputs(logits, _u8_labels("wce", labels))
     N, C, H, W = logits.shape
     if class_w.dtype != torch.float32 or class_w.numel() != C or class_w.device != logits.device:
         raise ValueError("wce: class_w must hold %d fp32 weights on %s" % (C, logits.device))
@@ -2238,7 +2239,7 @@ class WceFn(torch.autograd.Function):
         lstride, post, w0, sigma = ctx.cfg
         N, C, H, W = logits.shape
         d = torch.empty_like(logits)
-        gs = gout.reshape(1).to(torch.float32).contiguous()
+        gs = _gscale(gout)
         call("xv2_wce_backward", logits, labels, N, C, H, W, lstride, 1 if post else 0, class_w, d1, d2, w0, sigma, sums, gs, d)
         return (d,) + (None,) * 8
 
