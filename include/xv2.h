@@ -1145,6 +1145,37 @@ int xv2_split_seed(const uint8_t* mask, int B, int H, int W, int r2, void* works
 int xv2_split_grow(const uint8_t* mask, int B, int H, int W, int sweeps, void* workspace, int32_t* pending, void* stream);
 int xv2_split_finish(const uint8_t* mask, int B, int H, int W, void* workspace, uint8_t* out, int32_t* labels, void* stream);
 
+/* ---- clean buildings: fill small holes, drop small buildings (clean.hip, xview2_amd/utils/clean.py) ------------------------
+ * Per tile, pre is uint8 [H,W] and a pixel is building iff its value != 0; post is an optional uint8 [H,W];
+ * min_area = A >= 0 and max_hole = M >= 0 are integers.
+ * Stage 1, fill.  A hole is an 8-connected component of background pixels none of which lies on the tile's outer frame
+ * (y == 0, y == H - 1, x == 0, x == W - 1).  Its area is its number of pixels; islands of building inside it do not count.
+ * A hole is filled iff 1 <= area <= M.  A filled pixel gets pre = 1.  The hole's owner is the 4-connected building, in the
+ * unfilled map, that holds the pixel immediately left of the hole's first pixel in raster order: that pixel is always
+ * building, and it belongs to the enclosing building, never to an island.  A filled pixel gets post = the owner's voted class:
+ * the class 1..4 with the most pixels among the owner's pixels in the unfilled post, ties to the smaller class (the rule of
+ * xv2_postprocess with components), and 0 if the owner has no pixel in 1..4.
+ * Stage 2, drop.  The 4-connected components of the FILLED pre map are labelled: an island inside a filled hole has thereby
+ * merged with its owner, and filled pixels count towards area.  A component with area < A is dropped: pre = 0 and post = 0
+ * on its pixels.  Every other pixel keeps its input bytes.
+ * stats: device int64 [B][4], overwritten by every call: holes filled, pixels filled, buildings dropped, pixels dropped.
+ * A = 0 and M = 0 together are the identity (two device copies).  Any value above H * W is legal and means "all".
+ * Background goes by 8-connectivity, the dual of 4-connected buildings and the notion of hole that xv2_polygon_trace rings:
+ * a courtyard joined to the outside only through a diagonal step is no hole, and a hole that touches the frame is never
+ * filled.
+ * post and post_out are both NULL or both set.  Outputs must not alias inputs; no input is written, and nothing is written
+ * outside pre_out, post_out, stats and the workspace.  The workspace (xv2_clean_workspace: 20 bytes per pixel, four uint32
+ * words per root and an int32 label; 0 outside the limits) must be 16-byte aligned and needs no clearing; it may be NULL when
+ * M == 0 and A <= 1.  Size limits as xv2_postprocess (H * W < 2^30, B <= 65535).  A negative A or M, a post without a
+ * post_out or the reverse, or a size outside the limits is XV2_EINVAL before anything is enqueued.
+ * Launches: four when M > 0 (label both kinds, merge region borders including the diagonal neighbours across edges and
+ * corners, compress + tally, fill), four when A > 1 (label, merge, compress + tally, drop); which of them run depends on A
+ * and M alone, never on the maps.  Nothing is read back, and every reduction is an integer add or min, so the bytes are the
+ * same on every run. */
+size_t xv2_clean_workspace(int B, int H, int W);
+int xv2_clean_buildings(const uint8_t* pre, const uint8_t* post, int B, int H, int W, int64_t min_area, int64_t max_hole,
+                        void* workspace, uint8_t* pre_out, uint8_t* post_out, int64_t* stats, void* stream);
+
 /* ---- register the post image to the pre image (align.hip, xview2_amd/utils/align.py) ---------------------------------------
  * An integer translation found by block matching.  All quantities are integers.
  * Luma.  Scenes are uint8 [B][H][W][3] in stored channel order (B, G, R).  Y = (29 c0 + 150 c1 + 77 c2 + 128) >> 8, in 0..255.

@@ -18,7 +18,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("XV2_LIB", os.path.join(_HERE, "libxv2.so"))
 SOURCES = ["errors.cpp", "igemm_conv.hip", "direct_conv.hip", "thin_conv.hip", "sg_conv.hip", "stem_conv.hip", "wgrad_conv.hip", "norm_act.hip", "pool.hip", "pointwise.hip",
-           "loss.hip", "pack.hip", "ohem.hip", "sort.hip", "lovasz.hip", "wce.hip", "optim.hip", "xchg.hip", "augment.hip", "zoom.hip", "autoaug.hip", "postproc.hip", "buildings.hip", "match.hip", "polygons.hip", "simplify.hip", "rasterize.hip", "split.hip", "align.hip", "scene.hip", "resize.hip", "layer_entry.cpp"]
+           "loss.hip", "pack.hip", "ohem.hip", "sort.hip", "lovasz.hip", "wce.hip", "optim.hip", "xchg.hip", "augment.hip", "zoom.hip", "autoaug.hip", "postproc.hip", "buildings.hip", "match.hip", "polygons.hip", "simplify.hip", "rasterize.hip", "split.hip", "clean.hip", "align.hip", "scene.hip", "resize.hip", "layer_entry.cpp"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"] + os.environ.get("XV2_EXTRA_FLAGS", "").split()
 
@@ -78,7 +78,7 @@ def lib():
                      "xv2_bn_tensor_stats_workspace", "xv2_bn_backward_workspace", "xv2_bn_act_head_backward_workspace", "xv2_bn_act_shortcut_backward_workspace", "xv2_splat_gap_workspace",
                      "xv2_loss_workspace", "xv2_ohem_workspace", "xv2_sort_workspace", "xv2_lovasz_workspace", "xv2_border_workspace", "xv2_wce_workspace", "xv2_xchg_bytes", "xv2_presplit_f16_bytes", "xv2_postprocess_workspace",
                      "xv2_autoaugment_workspace", "xv2_building_table_workspace", "xv2_building_match_workspace", "xv2_polygon_count_workspace",
-                     "xv2_polygon_trace_workspace", "xv2_polygon_simplify_workspace", "xv2_rasterize_workspace", "xv2_split_workspace", "xv2_align_workspace"):
+                     "xv2_polygon_trace_workspace", "xv2_polygon_simplify_workspace", "xv2_rasterize_workspace", "xv2_split_workspace", "xv2_clean_workspace", "xv2_align_workspace"):
             getattr(_lib, name).restype = ctypes.c_size_t
         _lib.xv2_conv2d_forward_stats_tiles.restype = ctypes.c_int64
         _lib.xv2_conv2d_forward_stats_tile_rows.restype = ctypes.c_int64

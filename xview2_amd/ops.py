@@ -2838,6 +2838,55 @@ def split_buildings(mask, r2, sweeps_per_call=8, return_labels=False):
     return (out, calls, labels) if return_labels else (out, calls)
 
 
+# ---- fill small holes, drop small buildings (csrc/clean.hip) ---------------------------------------------------------------
+_INT64_MAX = (1 << 63) - 1
+
+
+def clean_workspace(B, H, W, device):
+    """uint8 workspace of xv2_clean_buildings from torch's caching allocator (a caller running many batches may keep it)"""
+    n = int(query("xv2_clean_workspace", int(B), int(H), int(W)))
+    if n == 0:
+        raise ValueError("clean_buildings: B=%d H=%d W=%d outside the supported sizes (H*W < 2^30, B <= 65535)" % (B, H, W))
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+def clean_buildings(pre, post=None, min_area=0, max_hole=0, workspace=None):
+    """Fill holes of at most max_hole pixels, then drop buildings of fewer than min_area pixels (include/xv2.h, "clean
+    buildings"): pre uint8 [B,H,W] (building iff != 0), post uint8 [B,H,W] or None.  workspace: None or a uint8 CUDA tensor of
+    at least clean_workspace() bytes, 16-byte aligned.  Returns (pre', post' or None, stats int64 [B,4] on the device: holes
+    filled, pixels filled, buildings dropped, pixels dropped).  Nothing is read back."""
+    _need_cuda(pre)
+    if pre.dim() != 3 or pre.dtype not in (torch.uint8, torch.bool):
+        raise ValueError("clean_buildings: pre must be uint8 [B,H,W], got %s %s" % (pre.dtype, tuple(pre.shape)))
+    if post is not None:
+        _need_cuda(post)
+        if post.dtype != torch.uint8 or post.shape != pre.shape:
+            raise ValueError("clean_buildings: post must be uint8 of pre's shape %s, got %s %s"
+                             % (tuple(pre.shape), post.dtype, tuple(post.shape)))
+        post = post.contiguous()
+    min_area, max_hole = int(min_area), int(max_hole)
+    if min_area < 0 or max_hole < 0:
+        raise ValueError("clean_buildings: min_area and max_hole must not be negative, got %d and %d" % (min_area, max_hole))
+    min_area, max_hole = min(min_area, _INT64_MAX), min(max_hole, _INT64_MAX)    # anything above H * W means "all"
+    pre = pre.to(torch.uint8).contiguous()
+    B, H, W = (int(v) for v in pre.shape)
+    need = int(query("xv2_clean_workspace", B, H, W))
+    if need == 0:
+        raise ValueError("clean_buildings: B=%d H=%d W=%d outside the supported sizes (H*W < 2^30, B <= 65535)" % (B, H, W))
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=pre.device)
+    elif (workspace.dtype != torch.uint8 or workspace.device != pre.device or not workspace.is_contiguous()
+          or workspace.numel() < need or workspace.data_ptr() % 16):
+        raise ValueError("clean_buildings: workspace must be a contiguous uint8 tensor on %s of at least %d bytes, 16-byte "
+                         "aligned (got %s %s, %d bytes)" % (pre.device, need, workspace.dtype, workspace.device,
+                                                            workspace.numel()))
+    pre_out = torch.empty_like(pre)
+    post_out = torch.empty_like(post) if post is not None else None
+    stats = torch.empty((B, 4), dtype=torch.int64, device=pre.device)
+    call("xv2_clean_buildings", pre, post, B, H, W, min_area, max_hole, workspace, pre_out, post_out, stats)
+    return pre_out, post_out, stats
+
+
 # ---- register the post image to the pre image (csrc/align.hip) ------------------------------------------------------------
 def _align_scene(what, name, t):
     _need_cuda(t)

@@ -12,7 +12,9 @@ damage class, pixel counts, confidence) and <stem>_buildings.json (totals), comp
 map (xview2_amd.utils.polygons), with the table's row as properties; it implies --buildings.  --simplify T
 reduces those outlines by Douglas-Peucker with a tolerance of T pixels, on the GPU; it changes the GeoJSON only.  --split R cuts the localization
 map where buildings touch (xview2_amd.utils.split) before any of these outputs is made: the PNGs, the table and the outlines
-all come from the split maps.  --align R registers the post scene to the pre scene first (xview2_amd.utils.align): the
+all come from the split maps.  --fill_holes M and --min_area A (xview2_amd.utils.clean) fill holes of at most M pixels inside
+buildings and then drop buildings of fewer than A pixels, before the split: the PNGs, the table, its JSON (which then lists what
+was filled and dropped under "clean") and the outlines all come from the cleaned maps.  --align R registers the post scene to the pre scene first (xview2_amd.utils.align): the
 best whole-pixel translation within R pixels is found and applied on the GPU before the damage model sees the pair, and
 <stem>_alignment.json reports the shift, the residuals and how far the tiles of the scene agree with it.  --scales s1,s2,...
 predicts every scene once per scale and averages the maps (xview2_amd.scene, predict(scales=...)): the scene is resized on the
@@ -53,6 +55,10 @@ def get_parser():
         "pixels of what is left (Douglas-Peucker per ring, 0 <= T < 4096); 0 = off.  No value is recommended")
     arg("--split", type=int, default=0, metavar="R", help="cut buildings that touch: erosion radius in pixels, 0 = off; applied "
         "after --dilate (a dilation after it would close the cuts again) and before the vote of --components")
+    arg("--min_area", type=int, default=0, metavar="A", help="drop predicted buildings of fewer than A pixels, 0 = off; applied "
+        "after --fill_holes and before --split.  No value is recommended")
+    arg("--fill_holes", type=int, default=0, metavar="M", help="fill holes of at most M pixels inside predicted buildings (a "
+        "hole is 8-connected background that does not touch the scene's frame), 0 = off.  No value is recommended")
     arg("--align", type=int, default=0, metavar="R", help="register the post scene to the pre scene before the damage model "
         "reads the pair: the best whole-pixel translation with |dy|, |dx| <= R (1..32) is applied to the post scene and "
         "<stem>_alignment.json is written; 0 = off.  A shift found at the limit R (at_limit in the report) means the true "
@@ -129,6 +135,10 @@ def main(argv=None):
     if args.simplify:
         from .utils.polygons import quantise_tolerance
         quantise_tolerance(args.simplify)
+    if args.min_area or args.fill_holes:
+        from .utils.clean import check_fill_holes, check_min_area
+        check_min_area(args.min_area)
+        check_fill_holes(args.fill_holes)
     pairs = pair_inputs(args.pre, args.post if args.ckpt_dmg is not None or args.align else None)
     if not torch.cuda.is_available():
         raise RuntimeError("xview2_amd.predict runs on the MI355X only; there is no CPU fallback")
@@ -167,8 +177,9 @@ def main(argv=None):
         loc_map = loc_maps[0] if loc is not None else torch.ones((H, W), dtype=torch.float32, device=device)
         dmg_map = (scene.decode_damage(dmg_maps, dmg.kind) if dmg is not None
                    else torch.ones((H, W), dtype=torch.int32, device=device))
-        pre_png, post_png = post_process_tiles(loc_map, dmg_map, args.components and dmg is not None, args.dilate,
-                                               args.dilation_rate, split=args.split)
+        pre_png, post_png, clean_stats = post_process_tiles(loc_map, dmg_map, args.components and dmg is not None, args.dilate,
+                                                            args.dilation_rate, split=args.split, min_area=args.min_area,
+                                                            fill_holes=args.fill_holes, return_stats=True)
         if loc is not None:
             Image.fromarray(pre_png.cpu().numpy()).save(stem + "_localization_prediction.png")
         if dmg is not None:
@@ -180,7 +191,16 @@ def main(argv=None):
                                                     return_labels=True)
             records = buildings.to_records(rows, H, W, confidence=loc is not None)
             buildings.write_csv(stem + "_buildings.csv", records)
-            buildings.write_summary(stem + "_buildings.json", records)
+            if clean_stats is not None:      # only with --min_area / --fill_holes: the JSON is otherwise what it was
+                import json
+                from .utils import clean
+                doc = buildings.summary(records)
+                doc["clean"] = clean.totals(clean_stats)
+                with open(stem + "_buildings.json", "w") as f:
+                    json.dump(doc, f, indent=1, sort_keys=True)
+                    f.write("\n")
+            else:
+                buildings.write_summary(stem + "_buildings.json", records)
             if args.polygons:
                 from .utils import polygons
                 polygons.write_geojson(stem + "_buildings.geojson", polygons.building_polygons(pre_png, labels, args.simplify),

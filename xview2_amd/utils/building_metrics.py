@@ -12,11 +12,14 @@ What this does not do:
   * Labelled buildings that touch in the raster are ONE building here: the target PNG carries no instance ids.
     --split_targets R cuts them apart by shape (utils/split.py) before they are labelled, --split R does the same to the
     prediction; neither knows the labelled instances.
-  * There is no minimum-area filter: a one-pixel component is a building on either side.
+  * The minimum-area filter is off unless asked for: by default a one-pixel component is a building on either side.
+    --min_area A / --fill_holes M clean the predicted pair (utils/clean.py: holes of at most M pixels filled, then
+    buildings below A pixels dropped) and --min_area_targets A drops small labelled buildings, each before the split.
   * There is no georeferencing: boxes and ids are pixel coordinates and row numbers of the tile.
 
     python -m xview2_amd.utils.building_metrics PRED_DIR TARG_DIR OUT_JSON [--iou 1/2] [--per_building DIR] [--batch 16]
-                                                [--split R] [--split_targets R]
+                                                [--split R] [--split_targets R] [--min_area A] [--fill_holes M]
+                                                [--min_area_targets A]
 """
 import json
 import os
@@ -206,12 +209,18 @@ class BuildingMetrics:
 
     get_path_handlers = XviewMetrics.get_path_handlers      # the same file naming, through the same PathHandler
 
-    def __init__(self, pred_dir, targ_dir, iou=(1, 2), batch=16, split=0, split_targets=0):
+    def __init__(self, pred_dir, targ_dir, iou=(1, 2), batch=16, split=0, split_targets=0, min_area=0, fill_holes=0,
+                 min_area_targets=0):
         self.pred_dir, self.targ_dir = Path(pred_dir), Path(targ_dir)
         assert self.pred_dir.is_dir(), "Could not find prediction directory: '%s'" % pred_dir
         assert self.targ_dir.is_dir(), "Could not find target directory: '%s'" % targ_dir
         self.iou, self.batch = (int(iou[0]), int(iou[1])), batch
         self.split, self.split_targets = int(split), int(split_targets)
+        self.min_area, self.fill_holes, self.min_area_targets = min_area, fill_holes, min_area_targets
+        if min_area or fill_holes or min_area_targets:
+            from .clean import check_fill_holes, check_min_area
+            self.min_area, self.fill_holes = check_min_area(min_area), check_fill_holes(fill_holes)
+            self.min_area_targets = check_min_area(min_area_targets)
         self.get_path_handlers()
         self.get_matches()
         self.counts = [tile_counts(tm) for tm in self.matches]
@@ -233,6 +242,12 @@ class BuildingMetrics:
             for i in range(0, len(self.path_handlers), self.batch):
                 tiles = list(pool.map(_load, self.path_handlers[i:i + self.batch]))
                 lp, dp, lt, dt = (torch.from_numpy(np.stack([t[k] for t in tiles])).to(dev) for k in range(4))
+                if self.min_area or self.fill_holes or self.min_area_targets:
+                    from .clean import clean_maps
+                    if self.min_area or self.fill_holes:
+                        lp, dp = clean_maps(lp, dp, self.min_area, self.fill_holes)
+                    if self.min_area_targets:
+                        lt, dt = clean_maps(lt, dt, self.min_area_targets, 0)
                 if self.split or self.split_targets:
                     from .split import split_maps
                     if self.split:
@@ -255,11 +270,13 @@ class BuildingMetrics:
         return paths
 
     @classmethod
-    def compute_score(cls, pred_dir, targ_dir, out_fp, iou=(1, 2), per_building=None, batch=16, split=0, split_targets=0):
+    def compute_score(cls, pred_dir, targ_dir, out_fp, iou=(1, 2), per_building=None, batch=16, split=0, split_targets=0,
+                      min_area=0, fill_holes=0, min_area_targets=0):
         """write the object-level metrics JSON to out_fp (and the per-building CSVs into per_building, when given); batch:
         tiles per call of the kernels; split, split_targets: radius of utils.split on the predicted and on the labelled pair
-        before the buildings are labelled (0 = off)"""
-        self = cls(pred_dir, targ_dir, iou, batch, split, split_targets)
+        before the buildings are labelled (0 = off); min_area, fill_holes: utils.clean on the predicted pair, min_area_targets:
+        its minimum area on the labelled pair, each before the split (0 = off)"""
+        self = cls(pred_dir, targ_dir, iou, batch, split, split_targets, min_area, fill_holes, min_area_targets)
         d = self.score_dict()
         with open(out_fp, "w") as f:
             json.dump(d, f, indent=1, sort_keys=True)
@@ -292,10 +309,17 @@ def get_parser():
                    "erosion radius in pixels, 0 = off")
     p.add_argument("--split_targets", type=int, default=0, metavar="R", help="the same for the labelled buildings, so that "
                    "touching labelled buildings count separately")
+    p.add_argument("--min_area", type=int, default=0, metavar="A", help="drop predicted buildings of fewer than A pixels before "
+                   "labelling (and before --split), 0 = off")
+    p.add_argument("--fill_holes", type=int, default=0, metavar="M", help="fill holes of at most M pixels inside predicted "
+                   "buildings first, 0 = off")
+    p.add_argument("--min_area_targets", type=int, default=0, metavar="A", help="drop labelled buildings of fewer than A pixels "
+                   "before labelling (and before --split_targets), 0 = off")
     return p
 
 
 if __name__ == "__main__":
     a = get_parser().parse_args()
     compute_score(os.path.expanduser(a.pred_dir), os.path.expanduser(a.targ_dir), os.path.expanduser(a.out_fp), a.iou,
-                  os.path.expanduser(a.per_building) if a.per_building else None, a.batch, a.split, a.split_targets)
+                  os.path.expanduser(a.per_building) if a.per_building else None, a.batch, a.split, a.split_targets,
+                  a.min_area, a.fill_holes, a.min_area_targets)

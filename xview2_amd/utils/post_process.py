@@ -19,7 +19,7 @@ Semantics are the reference's (post_process.py:27-47), bit for bit, with these d
      ValueError, where the reference would vote over it and write a PNG its scorer rejects.
 
     python -m xview2_amd.utils.post_process --results R [--components] [--dilate [--dilation_rate 3]] [--split R]
-                                            [--buildings] [--polygons [--simplify T]]
+                                            [--min_area A] [--fill_holes M] [--buildings] [--polygons [--simplify T]]
 
 --buildings also writes buildings/test_buildings_NNNNN.csv per pair: one row per predicted building of the two PNGs
 (xview2_amd.utils.buildings), its confidence from the localization probabilities.  --polygons (which implies --buildings)
@@ -28,7 +28,9 @@ adds buildings/test_buildings_NNNNN.geojson: the outline of every building, trac
 GeoJSON only.  --split R cuts the localization map where buildings touch (xview2_amd.utils.split: erosion
 by a disc of radius R, cores grown back, a 1-pixel cut where they meet) and masks the damage map with it.  The order is fuse,
 dilate, split, vote: a dilation after the split would close the cuts again, and the vote of --components is then taken per
-split piece.  The PNGs, the CSV and the GeoJSON all come from the split maps.
+split piece.  The PNGs, the CSV and the GeoJSON all come from the split maps.  --fill_holes M fills holes of at most M pixels
+inside buildings and --min_area A then drops buildings of fewer than A pixels (xview2_amd.utils.clean), both before the split:
+the order is fuse, dilate, clean, split, vote.  Both default to 0 = off, and then no call and no byte changes.
 """
 import os
 from argparse import ArgumentDefaultsHelpFormatter, ArgumentParser, ArgumentTypeError
@@ -50,24 +52,36 @@ def _check_rate(dilate, dilation_rate):
     return r
 
 
-def post_process_tiles(loc, dmg, components=False, dilate=False, dilation_rate=3, workspace=None, split=0):
+def post_process_tiles(loc, dmg, components=False, dilate=False, dilation_rate=3, workspace=None, split=0, min_area=0,
+                       fill_holes=0, return_stats=False):
     """uint8 (pre, post) on the device.  loc: fp32 [H,W] or [B,H,W]; dmg: [4|5,H,W] / [B,4|5,H,W] probabilities or an
     [H,W] / [B,H,W] label map.  Unbatched input gives unbatched output.  split > 0: fuse and dilate first, cut pre where
     buildings touch (utils.split.split_maps with that radius) and mask post with it, and only then, with components, vote
-    per split piece: a second pass over the split maps (pre' as the localization, post' as a label map, no dilation)."""
+    per split piece: a second pass over the split maps (pre' as the localization, post' as a label map, no dilation).
+    min_area > 0 or fill_holes > 0: utils.clean.clean_maps after the dilation and before the split, so that filled roofs
+    erode as solid shapes and the pieces a split makes are not deleted afterwards; the vote is then taken on the cleaned
+    maps by the same second pass.  return_stats: a third value, the device int64 [B,4] (or [4]) of clean_maps, None
+    when neither is set."""
     rate = _check_rate(dilate, dilation_rate)
     single = loc.dim() == 2
     if single:
         loc, dmg = loc.unsqueeze(0), dmg.unsqueeze(0)
-    if split:
-        from .split import split_maps
+    stats = None
+    if split or min_area or fill_holes:
         pre, post = ops.postprocess(loc, dmg, components=False, rate=rate, workspace=workspace)
-        pre, post = split_maps(pre, post, split)
+        if min_area or fill_holes:
+            from .clean import clean_maps
+            pre, post, stats = clean_maps(pre, post, min_area, fill_holes, return_stats=True)
+        if split:
+            from .split import split_maps
+            pre, post = split_maps(pre, post, split)
         if components:
             pre, post = ops.postprocess(pre.float(), post.to(torch.int32), components=True, rate=0, workspace=workspace)
     else:
         pre, post = ops.postprocess(loc, dmg, components=components, rate=rate, workspace=workspace)
-    return (pre[0], post[0]) if single else (pre, post)
+    if single:
+        pre, post, stats = pre[0], post[0], (stats[0] if stats is not None else None)
+    return (pre, post, stats) if return_stats else (pre, post)
 
 
 def connected_components(mask):
@@ -109,7 +123,8 @@ def post_process(args, pre_path, post_path):
     dev = _device()
     loc, dmg = _to_device(np.load(pre_path), dev), _to_device(np.load(post_path), dev)
     pre, post = post_process_tiles(loc, dmg, args.components, args.dilate, args.dilation_rate,
-                                   split=getattr(args, "split", 0))
+                                   split=getattr(args, "split", 0), min_area=getattr(args, "min_area", 0),
+                                   fill_holes=getattr(args, "fill_holes", 0))
     _save(pre.cpu().numpy(), os.path.join(results, "predictions", _out_name(pre_path)))
     _save(post.cpu().numpy(), os.path.join(results, "predictions", _out_name(post_path)))
 
@@ -122,6 +137,10 @@ def run(args):
     if split:
         from .split import check_radius
         split = check_radius(split)
+    min_area, fill_holes = getattr(args, "min_area", 0), getattr(args, "fill_holes", 0)
+    if min_area or fill_holes:
+        from .clean import check_fill_holes, check_min_area
+        min_area, fill_holes = check_min_area(min_area), check_fill_holes(fill_holes)
     if args.batch < 1:
         raise ValueError("--batch must be >= 1, got %d" % args.batch)
     simplify = getattr(args, "simplify", 0.0)
@@ -152,7 +171,7 @@ def run(args):
                 if key not in workspace and (args.components or rate):
                     workspace[key] = ops.postprocess_workspace(len(ks), lshape[0], lshape[1], args.components, dev)
                 pre, post = post_process_tiles(loc, dmg, args.components, args.dilate, args.dilation_rate,
-                                               workspace.get(key), split=split)
+                                               workspace.get(key), split=split, min_area=min_area, fill_holes=fill_holes)
                 want_polygons = getattr(args, "polygons", False)
                 if getattr(args, "buildings", False) or want_polygons:
                     from . import buildings
@@ -199,6 +218,10 @@ def get_parser():
         "pixels of what is left (Douglas-Peucker per ring, 0 <= T < 4096); 0 = off.  No value is recommended")
     arg("--split", type=int, default=0, metavar="R", help="Cut buildings that touch: erosion radius in pixels, 0 = off.  "
         "Applied after --dilate (a dilation after it would close the cuts again) and before the vote of --components")
+    arg("--min_area", type=int, default=0, metavar="A", help="Drop predicted buildings of fewer than A pixels, 0 = off.  "
+        "Applied after --fill_holes and before --split.  No value is recommended")
+    arg("--fill_holes", type=int, default=0, metavar="M", help="Fill holes of at most M pixels inside predicted buildings (a "
+        "hole is 8-connected background that does not touch the tile's frame), 0 = off.  No value is recommended")
     return parser
 
 
