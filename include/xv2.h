@@ -908,6 +908,34 @@ size_t xv2_postprocess_workspace(int B, int H, int W, int components);
  * XV2_DMG_LABEL, may be NULL otherwise), so the caller can reject the result. */
 int xv2_postprocess(const float* loc, const void* dmg, int dmg_kind, int B, int H, int W, int components, int rate,
                     void* workspace, uint8_t* pre, uint8_t* post, int32_t* status, void* stream);
+/* xv2_postprocess with the fusion's constants as arguments: pre = (loc > t_loc) | ((loc > t_dmg) & (post > 1)), both
+ * compared in float32, and with class_scale (a HOST pointer to 4 floats, or NULL) post = 1 + the first maximum of the
+ * float32 products class_scale[c] * dmg[c] (each rounded once); NULL: no multiplication.  Everything after the fusion is
+ * xv2_postprocess's.  xv2_postprocess is this call with (0.3f, 0.1f, NULL).  A non-finite threshold, t_dmg > t_loc, a scale
+ * that is not finite and > 0, or scales with XV2_DMG_LABEL (a label map has no channels to scale) are XV2_EINVAL. */
+int xv2_postprocess_ex(const float* loc, const void* dmg, int dmg_kind, int B, int H, int W, int components, int rate,
+                       void* workspace, uint8_t* pre, uint8_t* post, int32_t* status, float t_loc, float t_dmg,
+                       const float* class_scale, void* stream);
+/* The joint histogram from which every point of a threshold / class-scale grid of xv2_postprocess_ex can be scored
+ * (calibrate.hip, xview2_amd/utils/calibrate.py).  loc, dmg, dmg_kind as xv2_postprocess reads them; lt, dt: uint8 [B,H,W],
+ * the localization and damage targets.  thresholds: DEVICE fp32 [n], 1 <= n <= 128, finite and strictly ascending (device
+ * memory is not read back: ops.calibrate_hist checks the host copy it uploads; a table out of order gives a histogram that
+ * means nothing, never a fault).  scales: DEVICE fp32 [S][4], finite and > 0 (checked by ops.calibrate_hist likewise),
+ * 1 <= S <= 64, or NULL for S = 1 and no multiplication; must be NULL for XV2_DMG_LABEL.  Per pixel and scale vector s:
+ *   k = #{ j : loc > thresholds[j] } in float32 (0..n; NaN gives 0; monotone, so loc > thresholds[j] <=> k > j),
+ *   r = post - 1 (0..3), post decoded as xv2_postprocess_ex decodes it with class_scale = scales[s],
+ *   t = lt > 0,  d = dt (0..4),
+ * and hist[s][k][r][t][d] += 1, hist int64 [S][n+1][4][2][5].  A pixel with lt > 4 or dt > 4, or for XV2_DMG_LABEL a value
+ * outside 1..4, adds to bad[0] (int64, once per pixel, not once per scale vector) and to no bin.  hist and bad are
+ * accumulated into, never cleared (as xv2_xview2_counts), so one histogram covers a dataset over many calls; integer adds
+ * make the result independent of the schedule.  Size limits as xv2_postprocess. */
+int xv2_calibrate_hist(const float* loc, const void* dmg, int dmg_kind, const uint8_t* lt, const uint8_t* dt, int B, int H,
+                       int W, const float* thresholds, int n, const float* scales, int S, int64_t* hist, int64_t* bad,
+                       void* stream);
+/* Measurement switch of scripts/bench_calibrate.py: how many rounds of per-wave combining of equal keys later
+ * xv2_calibrate_hist calls of the process make before every lane left adds its own one; 0: one LDS atomic per pixel (the
+ * naive form), negative: the built-in default.  Same histogram whatever the value; no product code sets it. */
+int xv2_calibrate_hist_rounds(int rounds);
 /* scipy.ndimage.label of mask != 0 (post_process.py:39) with the labels above, int32 [B,H,W] out.  workspace is
  * unused (may be NULL); labels is the union-find's own storage. */
 int xv2_label_components(const uint8_t* mask, int B, int H, int W, void* workspace, int32_t* labels, void* stream);

@@ -18,7 +18,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("XV2_LIB", os.path.join(_HERE, "libxv2.so"))
 SOURCES = ["errors.cpp", "igemm_conv.hip", "direct_conv.hip", "thin_conv.hip", "sg_conv.hip", "stem_conv.hip", "wgrad_conv.hip", "norm_act.hip", "pool.hip", "pointwise.hip",
-           "loss.hip", "pack.hip", "ohem.hip", "sort.hip", "lovasz.hip", "wce.hip", "optim.hip", "xchg.hip", "augment.hip", "zoom.hip", "autoaug.hip", "postproc.hip", "buildings.hip", "match.hip", "polygons.hip", "simplify.hip", "rasterize.hip", "split.hip", "clean.hip", "align.hip", "scene.hip", "resize.hip", "layer_entry.cpp"]
+           "loss.hip", "pack.hip", "ohem.hip", "sort.hip", "lovasz.hip", "wce.hip", "optim.hip", "xchg.hip", "augment.hip", "zoom.hip", "autoaug.hip", "postproc.hip", "calibrate.hip", "buildings.hip", "match.hip", "polygons.hip", "simplify.hip", "rasterize.hip", "split.hip", "clean.hip", "align.hip", "scene.hip", "resize.hip", "layer_entry.cpp"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"] + os.environ.get("XV2_EXTRA_FLAGS", "").split()
 

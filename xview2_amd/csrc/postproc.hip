@@ -19,7 +19,9 @@
 //   pp_vote_kernel      majority class per root, max over the clamped rate x rate window, uint8 outputs
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <cmath>
 #include "xv2_common.h"
+#include "fuse_px.h"
 
 namespace {
 
@@ -29,7 +31,10 @@ constexpr int MAX_HALO = 32;       // dilation rate <= 65
 constexpr int HT = 4096;           // LDS tally slots of pp_compress_kernel (>= pixels of a region)
 constexpr unsigned EMPTY = 0xffffffffu;
 
-enum { K_4CH = 0, K_5CH = 1, K_LABEL = 2, K_MASK = 3 };
+using xv2::K_4CH;
+using xv2::K_5CH;
+using xv2::K_LABEL;
+using xv2::K_MASK;
 
 __device__ __forceinline__ int ld_label(const int32_t* p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -78,27 +83,17 @@ __device__ __forceinline__ void g_union(int32_t* lab, int a, int b) {
     }
 }
 
-// post of the reference: argmax(dmg) + 1 over four fp32 channels, the first maximum on ties (np.argmax)
-__device__ __forceinline__ int argmax4(const float* d, int64_t plane) {
-    float m = d[0];
-    int k = 0;
-#pragma unroll
-    for (int c = 1; c < 4; ++c) {
-        const float v = d[c * plane];
-        if (v > m) { m = v; k = c; }
-    }
-    return k + 1;
-}
-
 // Fuse + local labelling.  KIND: K_4CH / K_5CH (fp32 [B,C,H,W]), K_LABEL (int32 [B,H,W] label map), K_MASK
 // (uint8 [B,H,W], connected components only: fg = mask != 0, no pre / post).  comp != 0: labels + zeroed counts.
 // A label-map value that survives the fusion (pre set) but cannot be represented - outside 0..255 for a uint8 PNG, or
 // outside 0..4 when voting (4 histogram slots per root) - becomes background and is counted in *status.
+// t_loc, t_dmg and cs are the fusion's two thresholds and class scales (fuse_px.h; unused by K_MASK).
 template <int KIND>
 __global__ void __launch_bounds__(256) pp_fuse_kernel(const float* __restrict__ loc, const void* __restrict__ dmg, int H,
                                                       int W, int comp, int32_t* __restrict__ labels,
                                                       uint4* __restrict__ counts, uint8_t* __restrict__ pre_o,
-                                                      uint8_t* __restrict__ post_o, int* __restrict__ status) {
+                                                      uint8_t* __restrict__ post_o, int* __restrict__ status,
+                                                      float t_loc, float t_dmg, xv2::ClassScale cs) {
     __shared__ int par[RG * RG];
     const int tid = threadIdx.x, lx = tid & (RG - 1), ly0 = tid >> 6;
     const int x0 = blockIdx.x * RG, y0 = blockIdx.y * RG, b = blockIdx.z;
@@ -114,16 +109,8 @@ __global__ void __launch_bounds__(256) pp_fuse_kernel(const float* __restrict__ 
             if (KIND == K_MASK) {
                 post = reinterpret_cast<const uint8_t*>(dmg)[p] != 0;
             } else {
-                int raw;
-                if (KIND == K_4CH)
-                    raw = argmax4(reinterpret_cast<const float*>(dmg) + (int64_t)b * 4 * hw + (p - base), hw);
-                else if (KIND == K_5CH)   // background channel dropped, the 4-channel rule on channels 1..4
-                    raw = argmax4(reinterpret_cast<const float*>(dmg) + (int64_t)b * 5 * hw + hw + (p - base), hw);
-                else
-                    raw = reinterpret_cast<const int32_t*>(dmg)[p];
-                const float l = loc[p];
-                // float32 comparisons, as numpy compares a float32 array with a Python float
-                const int pre = (l > 0.3f) || ((l > 0.1f) && raw > 1);
+                const int raw = xv2::decode_raw<KIND == K_MASK ? K_LABEL : KIND>(dmg, b, hw, p - base, cs);
+                const int pre = xv2::fuse_pre(loc[p], raw, t_loc, t_dmg);
                 post = pre ? raw : 0;
                 if (KIND == K_LABEL && (post < 0 || post > (comp ? 4 : 255))) {
                     bad = 1;
@@ -375,9 +362,22 @@ static int check_sizes(const char* what, int B, int H, int W) {
     return XV2_OK;
 }
 
-extern "C" int xv2_postprocess(const float* loc, const void* dmg, int dmg_kind, int B, int H, int W, int components,
-                               int rate, void* workspace, uint8_t* pre, uint8_t* post, int32_t* status, void* stream) {
+extern "C" int xv2_postprocess_ex(const float* loc, const void* dmg, int dmg_kind, int B, int H, int W, int components,
+                                  int rate, void* workspace, uint8_t* pre, uint8_t* post, int32_t* status, float t_loc,
+                                  float t_dmg, const float* class_scale, void* stream) {
     if (int rc = check_sizes("postprocess", B, H, W)) return rc;
+    XV2_CHECK_ARG(std::isfinite(t_loc) && std::isfinite(t_dmg), "postprocess: thresholds %g and %g must be finite",
+                  (double)t_loc, (double)t_dmg);
+    XV2_CHECK_ARG(t_dmg <= t_loc, "postprocess: the damage-gated threshold %g must not exceed the localization threshold %g",
+                  (double)t_dmg, (double)t_loc);
+    XV2_CHECK_ARG(!class_scale || dmg_kind != XV2_DMG_LABEL,
+                  "postprocess: class scales need damage probabilities, a label map has none to scale");
+    xv2::ClassScale cs = {{1.f, 1.f, 1.f, 1.f}, class_scale ? 1 : 0};
+    for (int c = 0; class_scale && c < 4; ++c) {
+        XV2_CHECK_ARG(std::isfinite(class_scale[c]) && class_scale[c] > 0.f,
+                      "postprocess: class scale %d is %g, must be finite and > 0", c + 1, (double)class_scale[c]);
+        cs.s[c] = class_scale[c];
+    }
     XV2_CHECK_ARG(dmg_kind == XV2_DMG_4CH || dmg_kind == XV2_DMG_5CH || dmg_kind == XV2_DMG_LABEL,
                   "postprocess: dmg_kind=%d unsupported (4- or 5-channel probabilities, or an int32 label map)", dmg_kind);
     XV2_CHECK_ARG(rate == 0 || (rate >= 1 && rate % 2 == 1 && rate <= 2 * MAX_HALO + 1),
@@ -406,13 +406,13 @@ extern "C" int xv2_postprocess(const float* loc, const void* dmg, int dmg_kind, 
     const double fuse_bytes = px * (4 + cin + 2 + (components ? 20 : 0));
     if (dmg_kind == XV2_DMG_4CH)
         XV2_LAUNCH(pp_kid(0), fuse_bytes, pp_fuse_kernel<K_4CH>, grid, dim3(256), 0, st, loc, dmg, H, W, comp, labels, counts,
-                   ipre, ipost, status);
+                   ipre, ipost, status, t_loc, t_dmg, cs);
     else if (dmg_kind == XV2_DMG_5CH)
         XV2_LAUNCH(pp_kid(0), fuse_bytes, pp_fuse_kernel<K_5CH>, grid, dim3(256), 0, st, loc, dmg, H, W, comp, labels, counts,
-                   ipre, ipost, status);
+                   ipre, ipost, status, t_loc, t_dmg, cs);
     else
         XV2_LAUNCH(pp_kid(0), fuse_bytes, pp_fuse_kernel<K_LABEL>, grid, dim3(256), 0, st, loc, dmg, H, W, comp, labels,
-                   counts, ipre, ipost, status);
+                   counts, ipre, ipost, status, t_loc, t_dmg, cs);
     if (components) {
         XV2_LAUNCH(pp_kid(1), 8.0 * 128 * grid.x * grid.y * B, pp_merge_kernel, grid, dim3(128), 0, st, labels, H, W);
         XV2_LAUNCH(pp_kid(2), px * 9, pp_compress_kernel<true>, grid, dim3(256), 0, st, labels, ipost, H, W,
@@ -426,6 +426,12 @@ extern "C" int xv2_postprocess(const float* loc, const void* dmg, int dmg_kind, 
     return XV2_OK;
 }
 
+extern "C" int xv2_postprocess(const float* loc, const void* dmg, int dmg_kind, int B, int H, int W, int components,
+                               int rate, void* workspace, uint8_t* pre, uint8_t* post, int32_t* status, void* stream) {
+    return xv2_postprocess_ex(loc, dmg, dmg_kind, B, H, W, components, rate, workspace, pre, post, status, 0.3f, 0.1f, nullptr,
+                              stream);
+}
+
 extern "C" int xv2_label_components(const uint8_t* mask, int B, int H, int W, void* workspace, int32_t* labels,
                                     void* stream) {
     (void)workspace;
@@ -435,7 +441,7 @@ extern "C" int xv2_label_components(const uint8_t* mask, int B, int H, int W, vo
     const dim3 grid((W + RG - 1) / RG, (H + RG - 1) / RG, B);
     const double px = (double)B * H * W;
     XV2_LAUNCH(pp_kid(0), px * 5, pp_fuse_kernel<K_MASK>, grid, dim3(256), 0, st, nullptr, mask, H, W, 1, labels, nullptr,
-               nullptr, nullptr, nullptr);
+               nullptr, nullptr, nullptr, 0.f, 0.f, xv2::ClassScale{{1.f, 1.f, 1.f, 1.f}, 0});
     XV2_LAUNCH(pp_kid(1), 8.0 * 128 * grid.x * grid.y * B, pp_merge_kernel, grid, dim3(128), 0, st, labels, H, W);
     XV2_LAUNCH(pp_kid(2), px * 8, pp_compress_kernel<false>, grid, dim3(256), 0, st, labels, nullptr, H, W, nullptr);
     return XV2_OK;

@@ -9,6 +9,7 @@ import os
 import weakref
 from types import SimpleNamespace
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -2511,13 +2512,48 @@ def postprocess_workspace(B, H, W, components, device):
     return torch.empty(max(int(n), 1), dtype=torch.uint8, device=device)
 
 
-def postprocess(loc, dmg, components=False, rate=0, workspace=None):
+REF_LOC_THRESHOLD, REF_DMG_THRESHOLD = 0.3, 0.1     # the reference's fusion (post_process.py:35), xv2_postprocess's constants
+
+
+def check_class_scale(scale):
+    """(s1, s2, s3, s4) as Python floats that are exact float32 values, finite and > 0; ValueError otherwise"""
+    try:
+        v = [float(x) for x in scale]
+    except (TypeError, ValueError):
+        raise ValueError("class_scale: four numbers expected, got %r" % (scale,))
+    if len(v) != 4:
+        raise ValueError("class_scale: four numbers expected, got %d" % len(v))
+    with np.errstate(over="ignore"):
+        v = [float(np.float32(x)) for x in v]
+    if not all(np.isfinite(x) and x > 0 for x in v):
+        raise ValueError("class_scale: every scale must be finite and > 0 (in float32), got %r" % (tuple(scale),))
+    return tuple(v)
+
+
+def check_fusion_thresholds(loc_threshold, dmg_threshold):
+    """(a, b) as float32-exact Python floats, None replaced by the reference's 0.3 / 0.1; finite, b <= a"""
+    a = REF_LOC_THRESHOLD if loc_threshold is None else loc_threshold
+    b = REF_DMG_THRESHOLD if dmg_threshold is None else dmg_threshold
+    with np.errstate(over="ignore"):
+        a, b = float(np.float32(a)), float(np.float32(b))
+    if not (np.isfinite(a) and np.isfinite(b)):
+        raise ValueError("fusion thresholds must be finite, got %r and %r" % (loc_threshold, dmg_threshold))
+    if b > a:
+        raise ValueError("the damage-gated threshold %r must not exceed the localization threshold %r" % (b, a))
+    return a, b
+
+
+def postprocess(loc, dmg, components=False, rate=0, workspace=None, loc_threshold=None, dmg_threshold=None,
+                class_scale=None):
     """utils/post_process.py:28-45 on a batch: loc fp32 [B,H,W]; dmg fp32 [B,4|5,H,W] probabilities or a [B,H,W]
     label map (any integer or float dtype, converted to int32 on the device).  Label-map values that survive the fusion
     must be representable: 0..255 (uint8 output), 0..4 with components; anything else raises ValueError (the kernel
     counts such pixels; values dropped by the fusion, e.g. an unclamped mse decode on background, are not checked).
     rate = 0: no dilation, else an odd square edge.  workspace: None or a uint8 CUDA tensor of at least
-    postprocess_workspace() bytes, 256-byte aligned.  Returns uint8 (pre, post), [B,H,W] each."""
+    postprocess_workspace() bytes, 256-byte aligned.  Returns uint8 (pre, post), [B,H,W] each.
+    loc_threshold a, dmg_threshold b, class_scale (s1..s4): the fusion becomes pre = (loc > a) | ((loc > b) & (post > 1)) with
+    post = argmax(s * dmg) + 1 (xv2_postprocess_ex; a missing threshold is the reference's 0.3 / 0.1, scales need
+    probabilities).  All three None: exactly the call to xv2_postprocess that was always made."""
     _need_cuda(loc)
     _need_cuda(dmg)
     if loc.dim() != 3:
@@ -2552,7 +2588,17 @@ def postprocess(loc, dmg, components=False, rate=0, workspace=None):
                                                                          workspace.device, workspace.numel()))
     pre = torch.empty((B, H, W), dtype=torch.uint8, device=loc.device)
     post = torch.empty_like(pre)
-    call("xv2_postprocess", loc, dmg, kind, B, H, W, 1 if components else 0, rate, workspace, pre, post, status)
+    if loc_threshold is None and dmg_threshold is None and class_scale is None:
+        call("xv2_postprocess", loc, dmg, kind, B, H, W, 1 if components else 0, rate, workspace, pre, post, status)
+    else:
+        a, b = check_fusion_thresholds(loc_threshold, dmg_threshold)
+        cs = None
+        if class_scale is not None:
+            if kind == 2:
+                raise ValueError("postprocess: class_scale needs damage probabilities; a label map has no channels to scale")
+            cs = (ctypes.c_float * 4)(*check_class_scale(class_scale))     # a host pointer, read before the call returns
+        call("xv2_postprocess_ex", loc, dmg, kind, B, H, W, 1 if components else 0, rate, workspace, pre, post, status,
+             a, b, ctypes.addressof(cs) if cs is not None else None)
     if status is not None:
         bad = int(status.item())
         if bad:
@@ -2560,6 +2606,75 @@ def postprocess(loc, dmg, components=False, rate=0, workspace=None):
                              "clamped first" % (bad, "1..4 (--components votes over four classes)" if components
                                                 else "0..255"))
     return pre, post
+
+
+CAL_MAX_THRESHOLDS, CAL_MAX_SCALES = 128, 64     # calibrate.hip MAX_T, MAX_S
+
+
+def check_thresholds(thresholds):
+    """float32 [n] numpy copy of a threshold table: 1 <= n <= 128, finite, strictly ascending in float32.  xv2_calibrate_hist
+    takes the table in device memory and cannot look at it, so this is where its order is checked."""
+    t = np.asarray(thresholds, dtype=np.float64).reshape(-1)
+    with np.errstate(over="ignore"):
+        t = t.astype(np.float32)
+    if not 1 <= t.size <= CAL_MAX_THRESHOLDS:
+        raise ValueError("calibrate_hist: %d thresholds, must be 1..%d" % (t.size, CAL_MAX_THRESHOLDS))
+    if not np.isfinite(t).all():
+        raise ValueError("calibrate_hist: thresholds must be finite")
+    if t.size > 1 and not (np.diff(t) > 0).all():
+        raise ValueError("calibrate_hist: thresholds must be strictly ascending in float32")
+    return np.ascontiguousarray(t)
+
+
+def calibrate_hist(loc, dmg, lt, dt, thresholds, scales=None, hist=None, bad=None):
+    """Joint histogram of a batch for the threshold / class-scale sweep (include/xv2.h xv2_calibrate_hist).  loc, dmg as
+    postprocess takes them; lt, dt uint8 [B,H,W] targets; thresholds: host sequence of n ascending values; scales: None or a
+    host [S,4] table, S <= 64.  hist (int64 [S, n+1, 4, 2, 5]) and bad (int64 [1]) are accumulated into when given, else
+    created zeroed.  Returns (hist, bad), on the device."""
+    _need_cuda(loc)
+    _need_cuda(dmg)
+    if loc.dim() != 3:
+        raise ValueError("calibrate_hist: loc must be [B,H,W], got %s" % (tuple(loc.shape),))
+    B, H, W = loc.shape
+    loc = loc.contiguous().float()
+    if dmg.dim() == 4 and tuple(dmg.shape) in ((B, 4, H, W), (B, 5, H, W)):
+        kind = 0 if dmg.shape[1] == 4 else 1
+        dmg = dmg.contiguous().float()
+    elif dmg.dim() == 3 and tuple(dmg.shape) == (B, H, W):
+        kind = 2
+        dmg = dmg.to(torch.int32).contiguous()
+    else:
+        raise ValueError("calibrate_hist: dmg %s fits neither [B,4|5,H,W] nor [B,H,W] for loc %s"
+                         % (tuple(dmg.shape), tuple(loc.shape)))
+    tg = []
+    for t in (lt, dt):
+        _need_cuda(t)
+        if t.dtype != torch.uint8 or tuple(t.shape) != (B, H, W):
+            raise ValueError("calibrate_hist: targets must be uint8 %s, got %s %s" % ((B, H, W), t.dtype, tuple(t.shape)))
+        tg.append(t.contiguous())
+    th = check_thresholds(thresholds)
+    n, S, sc = th.size, 1, None
+    if scales is not None:
+        if kind == 2:
+            raise ValueError("calibrate_hist: class scales need damage probabilities; a label map has no channels to scale")
+        sc = np.asarray(scales, dtype=np.float64)
+        if sc.ndim != 2 or sc.shape[1] != 4 or not 1 <= sc.shape[0] <= CAL_MAX_SCALES:
+            raise ValueError("calibrate_hist: scales must be [S,4] with 1 <= S <= %d, got %s" % (CAL_MAX_SCALES, sc.shape))
+        sc = np.array([check_class_scale(row) for row in sc], dtype=np.float32)
+        S = sc.shape[0]
+        sc = torch.from_numpy(sc).to(loc.device)
+    th = torch.from_numpy(th).to(loc.device)
+    shape = (S, n + 1, 4, 2, 5)
+    if hist is None:
+        hist = torch.zeros(shape, dtype=torch.int64, device=loc.device)
+    elif hist.dtype != torch.int64 or tuple(hist.shape) != shape or not hist.is_contiguous() or hist.device != loc.device:
+        raise ValueError("calibrate_hist: hist must be a contiguous int64 %s on %s" % (shape, loc.device))
+    if bad is None:
+        bad = torch.zeros(1, dtype=torch.int64, device=loc.device)
+    elif bad.dtype != torch.int64 or bad.numel() != 1 or bad.device != loc.device:
+        raise ValueError("calibrate_hist: bad must be one int64 on %s" % (loc.device,))
+    call("xv2_calibrate_hist", loc, dmg, kind, tg[0], tg[1], B, H, W, th, n, sc, S, hist, bad)
+    return hist, bad
 
 
 def label_components(mask):

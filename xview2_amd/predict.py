@@ -21,7 +21,10 @@ predicts every scene once per scale and averages the maps (xview2_amd.scene, pre
 GPU as Pillow's bicubic resize does it, predicted at that size, and the maps are brought back to the native grid, where the
 post-processing and every output stay; --save_probs writes the averaged maps.  One value other than 1 predicts imagery of
 another ground resolution (a model trained at 0.5 m per pixel reads a 0.3 m scene at --scales 0.6); --align runs before it, at
-the native size."""
+the native size.  --loc_threshold A, --loc_threshold_dmg B and --class_scale s1,s2,s3,s4 replace the constants of the fusion
+(a building where loc > A, or loc > B with a damage class above 1; the damage class the argmax of s * probabilities), and
+--calibration FILE.json takes them from a report of xview2_amd.utils.calibrate, explicit flags winning; scales need a softmax
+damage checkpoint.  Without them the reference's 0.3 / 0.1 / plain argmax apply, through the call that was always made."""
 import os
 from argparse import ArgumentDefaultsHelpFormatter, ArgumentParser
 
@@ -70,6 +73,8 @@ def get_parser():
         "Pillow), predicted at that size and the maps resampled back (bilinear); all outputs stay on the native grid.  One "
         "value is a ground-resolution correction: the ratio of the scene's metres per pixel to the training data's.  No "
         "value is recommended")
+    from .utils import fusion
+    fusion.add_flags(arg)
     return parser
 
 
@@ -139,6 +144,8 @@ def main(argv=None):
         from .utils.clean import check_fill_holes, check_min_area
         check_min_area(args.min_area)
         check_fill_holes(args.fill_holes)
+    from .utils import fusion
+    fuse_kw = fusion.resolve(args)
     pairs = pair_inputs(args.pre, args.post if args.ckpt_dmg is not None or args.align else None)
     if not torch.cuda.is_available():
         raise RuntimeError("xview2_amd.predict runs on the MI355X only; there is no CPU fallback")
@@ -155,6 +162,10 @@ def main(argv=None):
         dmg = scene.ScenePredictor(_load(args.ckpt_dmg, args.ema, args.tta, device), args.window, args.overlap, args.batch)
         if dmg.kind == scene.SIGMOID1:
             raise ValueError("%s is no damage (--type post) checkpoint" % args.ckpt_dmg)
+        if fuse_kw["class_scale"] is not None and dmg.kind != scene.SOFTMAX:
+            raise ValueError("--class_scale multiplies the damage probabilities before their argmax, but %s is a coral / mse "
+                             "checkpoint, which decodes to a label map with no per-class probabilities to scale"
+                             % args.ckpt_dmg)
     os.makedirs(args.out, exist_ok=True)
     for pre_path, post_path in pairs:
         pre = read_bgr(pre_path)
@@ -179,7 +190,7 @@ def main(argv=None):
                    else torch.ones((H, W), dtype=torch.int32, device=device))
         pre_png, post_png, clean_stats = post_process_tiles(loc_map, dmg_map, args.components and dmg is not None, args.dilate,
                                                             args.dilation_rate, split=args.split, min_area=args.min_area,
-                                                            fill_holes=args.fill_holes, return_stats=True)
+                                                            fill_holes=args.fill_holes, return_stats=True, **fuse_kw)
         if loc is not None:
             Image.fromarray(pre_png.cpu().numpy()).save(stem + "_localization_prediction.png")
         if dmg is not None:

@@ -31,6 +31,10 @@ dilate, split, vote: a dilation after the split would close the cuts again, and 
 split piece.  The PNGs, the CSV and the GeoJSON all come from the split maps.  --fill_holes M fills holes of at most M pixels
 inside buildings and --min_area A then drops buildings of fewer than A pixels (xview2_amd.utils.clean), both before the split:
 the order is fuse, dilate, clean, split, vote.  Both default to 0 = off, and then no call and no byte changes.
+--loc_threshold A, --loc_threshold_dmg B and --class_scale s1,s2,s3,s4 (utils/fusion.py) replace the fusion's constants:
+pre = (loc > A) | ((loc > B) & (post > 1)), post = argmax(s * dmg) + 1; --calibration FILE.json takes them from a report of
+xview2_amd.utils.calibrate, explicit flags winning.  Without any of them the reference's 0.3 / 0.1 / no scales apply through
+the call that was always made.
 """
 import os
 from argparse import ArgumentDefaultsHelpFormatter, ArgumentParser, ArgumentTypeError
@@ -41,6 +45,7 @@ import numpy as np
 import torch
 
 from .. import ops
+from . import fusion
 
 
 def _check_rate(dilate, dilation_rate):
@@ -53,7 +58,7 @@ def _check_rate(dilate, dilation_rate):
 
 
 def post_process_tiles(loc, dmg, components=False, dilate=False, dilation_rate=3, workspace=None, split=0, min_area=0,
-                       fill_holes=0, return_stats=False):
+                       fill_holes=0, return_stats=False, loc_threshold=None, dmg_threshold=None, class_scale=None):
     """uint8 (pre, post) on the device.  loc: fp32 [H,W] or [B,H,W]; dmg: [4|5,H,W] / [B,4|5,H,W] probabilities or an
     [H,W] / [B,H,W] label map.  Unbatched input gives unbatched output.  split > 0: fuse and dilate first, cut pre where
     buildings touch (utils.split.split_maps with that radius) and mask post with it, and only then, with components, vote
@@ -61,14 +66,18 @@ def post_process_tiles(loc, dmg, components=False, dilate=False, dilation_rate=3
     min_area > 0 or fill_holes > 0: utils.clean.clean_maps after the dilation and before the split, so that filled roofs
     erode as solid shapes and the pieces a split makes are not deleted afterwards; the vote is then taken on the cleaned
     maps by the same second pass.  return_stats: a third value, the device int64 [B,4] (or [4]) of clean_maps, None
-    when neither is set."""
+    when neither is set.  loc_threshold, dmg_threshold, class_scale (ops.postprocess) apply to the fusing pass only: the
+    second pass reads a 0/1 map as its localization and keeps the defaults."""
+    # only what was given: with the defaults ops.postprocess gets the call it always got
+    fuse_kw = {k: v for k, v in (("loc_threshold", loc_threshold), ("dmg_threshold", dmg_threshold),
+                                ("class_scale", class_scale)) if v is not None}
     rate = _check_rate(dilate, dilation_rate)
     single = loc.dim() == 2
     if single:
         loc, dmg = loc.unsqueeze(0), dmg.unsqueeze(0)
     stats = None
     if split or min_area or fill_holes:
-        pre, post = ops.postprocess(loc, dmg, components=False, rate=rate, workspace=workspace)
+        pre, post = ops.postprocess(loc, dmg, components=False, rate=rate, workspace=workspace, **fuse_kw)
         if min_area or fill_holes:
             from .clean import clean_maps
             pre, post, stats = clean_maps(pre, post, min_area, fill_holes, return_stats=True)
@@ -78,7 +87,7 @@ def post_process_tiles(loc, dmg, components=False, dilate=False, dilation_rate=3
         if components:
             pre, post = ops.postprocess(pre.float(), post.to(torch.int32), components=True, rate=0, workspace=workspace)
     else:
-        pre, post = ops.postprocess(loc, dmg, components=components, rate=rate, workspace=workspace)
+        pre, post = ops.postprocess(loc, dmg, components=components, rate=rate, workspace=workspace, **fuse_kw)
     if single:
         pre, post, stats = pre[0], post[0], (stats[0] if stats is not None else None)
     return (pre, post, stats) if return_stats else (pre, post)
@@ -124,9 +133,26 @@ def post_process(args, pre_path, post_path):
     loc, dmg = _to_device(np.load(pre_path), dev), _to_device(np.load(post_path), dev)
     pre, post = post_process_tiles(loc, dmg, args.components, args.dilate, args.dilation_rate,
                                    split=getattr(args, "split", 0), min_area=getattr(args, "min_area", 0),
-                                   fill_holes=getattr(args, "fill_holes", 0))
+                                   fill_holes=getattr(args, "fill_holes", 0), **fusion.resolve(args))
     _save(pre.cpu().numpy(), os.path.join(results, "predictions", _out_name(pre_path)))
     _save(post.cpu().numpy(), os.path.join(results, "predictions", _out_name(post_path)))
+
+
+def prob_pairs(results):
+    """(localization files, damage files) under <results>/probs, sorted: the k-th of each is one pair (as the reference)"""
+    pre_paths = sorted(glob(os.path.join(results, "probs", "*localization*")))
+    post_paths = sorted(glob(os.path.join(results, "probs", "*damage*")))
+    if len(pre_paths) != len(post_paths):
+        raise ValueError("%d localization files but %d damage files" % (len(pre_paths), len(post_paths)))
+    return pre_paths, post_paths
+
+
+def geometry_groups(locs, dmgs):
+    """(loc shape, dmg shape, dmg dtype) -> indices: one launch per input geometry"""
+    groups = {}
+    for k, (l, d) in enumerate(zip(locs, dmgs)):
+        groups.setdefault((l.shape, d.shape, d.dtype.str), []).append(k)
+    return groups
 
 
 def run(args):
@@ -147,12 +173,10 @@ def run(args):
     if simplify:
         from .polygons import quantise_tolerance
         quantise_tolerance(simplify)
+    fuse_kw = fusion.resolve(args)
     pred_dir = os.path.join(args.results, "predictions")
     os.makedirs(pred_dir, exist_ok=True)
-    pre_paths = sorted(glob(os.path.join(args.results, "probs", "*localization*")))
-    post_paths = sorted(glob(os.path.join(args.results, "probs", "*damage*")))
-    if len(pre_paths) != len(post_paths):
-        raise ValueError("%d localization files but %d damage files" % (len(pre_paths), len(post_paths)))
+    pre_paths, post_paths = prob_pairs(args.results)
     dev = _device()
     workspace = {}
     with ThreadPoolExecutor(max_workers=4) as pool:
@@ -161,17 +185,15 @@ def run(args):
             pairs = list(zip(pre_paths[i:i + args.batch], post_paths[i:i + args.batch]))
             locs = [np.load(a) for a, _ in pairs]
             dmgs = [np.load(b) for _, b in pairs]
-            groups = {}
-            for k, (l, d) in enumerate(zip(locs, dmgs)):   # one launch per input geometry
-                groups.setdefault((l.shape, d.shape, d.dtype.str), []).append(k)
-            for (lshape, _, _), ks in groups.items():
+            for (lshape, _, _), ks in geometry_groups(locs, dmgs).items():
                 loc = _to_device(np.stack([locs[k] for k in ks]), dev)
                 dmg = _to_device(np.stack([dmgs[k] for k in ks]), dev)
                 key = (len(ks),) + tuple(lshape)
                 if key not in workspace and (args.components or rate):
                     workspace[key] = ops.postprocess_workspace(len(ks), lshape[0], lshape[1], args.components, dev)
                 pre, post = post_process_tiles(loc, dmg, args.components, args.dilate, args.dilation_rate,
-                                               workspace.get(key), split=split, min_area=min_area, fill_holes=fill_holes)
+                                               workspace.get(key), split=split, min_area=min_area, fill_holes=fill_holes,
+                                               **fuse_kw)
                 want_polygons = getattr(args, "polygons", False)
                 if getattr(args, "buildings", False) or want_polygons:
                     from . import buildings
@@ -222,6 +244,7 @@ def get_parser():
         "Applied after --fill_holes and before --split.  No value is recommended")
     arg("--fill_holes", type=int, default=0, metavar="M", help="Fill holes of at most M pixels inside predicted buildings (a "
         "hole is 8-connected background that does not touch the tile's frame), 0 = off.  No value is recommended")
+    fusion.add_flags(arg)
     return parser
 
 
